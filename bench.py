@@ -13,11 +13,15 @@ BCE, backward through D into G, clip, optimiser).  Inputs are resident in HBM be
 timed region.  N > 1: pure data parallelism, one process per GPU, one RCCL all-reduce per
 network per step (weak scaling: per-GPU batch fixed).
 
-Rank 0 prints ONE JSON line (contract in the task description) with two extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints it;
+--dump-outputs DIR also writes what the last timed step computed (see dump_outputs).  --full adds:
   roofline     -- the kernel class with the largest share of GPU time, timed live with HIP
-                  events on the launch stream during the timed steps
+                  events on the launch stream during the timed steps (plus the conv_stack /
+                  gemm_class / kernel_table objects of the same profiled warm-up step)
+  replay_check -- one more graph replay against one eager step from the same state
   cpu_baseline -- the CPU oracle (oracle/audiogan_oracle.py, kind "port") running the same
                   step on a bounded sample of the workload on this host's cores
+(--workload full: the eager profiling pass, the replay / host breakdown and its cpu_baseline).
 """
 import argparse
 import json
@@ -25,6 +29,7 @@ import os
 import sys
 import time
 import warnings
+import zlib
 
 warnings.filterwarnings('ignore', category=FutureWarning)
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -103,6 +108,29 @@ def one_step(train, g, d, opt_g, opt_d, b, hook_d=None, hook_g=None, overlap=Fal
                                   hook_d=hook_d, hook_g=hook_g)
     return train.gd_step(g, d, opt_g, opt_d, b['real'], b['real_len'], b['c'], b['z'], b['noise_real'],
                          b['noise_fake'], 1.0, 0.1, overlap=overlap, hook_d=hook_d, hook_g=hook_g)
+
+
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(dirname, named):
+    """``named``: (name, tensor) pairs -> ``dirname/<name>.npy``, float32 (float64 tensors stay float64), at most DUMP_BUDGET
+    bytes in all.  When the whole set is larger, every tensor above a common element cap keeps only a fixed sample of that
+    many elements (sorted flat indices drawn with the CRC32 of its name as the seed), so two runs write the same elements."""
+    arrs = []
+    for name, t in named:
+        t = t.detach()
+        arrs.append((name, t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()))
+    budget = DUMP_BUDGET - 256 * len(arrs)           # (room for the .npy headers)
+    cap = max(a.size for _, a in arrs)
+    while sum(min(a.size, cap) * a.itemsize for _, a in arrs) > budget:
+        cap = cap * 9 // 10
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrs:
+        if a.size > cap:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def pmc_traffic(kernel, dtype='f32'):
@@ -234,28 +262,38 @@ def run_full(args, dev):
     for _ in range(max(args.warmup, 1)):
         lp.outer()
     torch.cuda.synchronize()
-    if lp.graphed:
+    if lp.graphed and args.full:
         lp.gpu_timeline = []
     h0 = dict(lp.host_ms)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        lp.outer()
+        last = lp.outer()
     t_issue = time.perf_counter() - t0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    _, rd, rg = last
+    finite = all(np.isfinite(v) for rec in lp.log for v in rec[2:])
+    if lp.graphed:       # the captured iterations keep their scalars on the device: read the last pass's once, after the timed region
+        finite = finite and all(np.isfinite(float(v)) for v in (rd['loss'], rd['acc_d'], rd['acc_g'], rg['loss'],
+                                                                 rg['feature_penalty'], rg['baseline']))
+    if args.dump_outputs:
+        outs = [('%s.%s' % (it, k), torch.as_tensor(v)) for it, r in (('critic', rd), ('generator', rg))
+                for k, v in r.items() if v is not None]
+        dump_outputs(args.dump_outputs, [(k, v) for k, v in outs if v.is_floating_point()] +
+                     [('%s.%s' % (m, k), p_) for m, net in zip(('g', 'd', 'e_g', 'e_d'), mods[:4])
+                      for k, p_ in net.named_parameters()])
     host_ms = {k: ((lp.host_ms[k] - h0.get(k, 0.0)) / args.steps if not k.endswith('_max') else lp.host_ms[k]) for k in lp.host_ms}
     # the same pass with device time only (launches enqueued back to back inside one profiler window): how much of the wall
     # time is the host issuing ~3000 launches
     prof, dev_ms = {}, None
-    if not lp.graphed:
+    if args.full and not lp.graphed:
         K.Profiler.start(only=None)
         lp.outer()
         prof = K.Profiler.stop()
         dev_ms = sum(v['ms'] for v in prof.values())
     status = K.lstm_persist_status(dev)
-    finite = all(np.isfinite(v) for rec in lp.log for v in rec[2:])
     extra = {}
-    if lp.graphed:
+    if args.full and lp.graphed:
         # where a pass's wall time goes: the three replays alone (inputs left as they are), and the host's share (loader +
         # pick_words for three minibatches), which the Feeder overlaps with the replays
         torch.cuda.synchronize()
@@ -277,10 +315,6 @@ def run_full(args, dev):
             for (k0, a0, b0, h0_), (k1, a1, b1, h1_) in zip(evs[-13:-1], evs[-12:]):
                 tl.append((k1, round(a1.elapsed_time(b1), 2), round(b0.elapsed_time(a1), 2), round((h1_ - h0_) * 1e3, 2)))
             extra['replay_timeline'] = {'columns': ['graph', 'gpu_ms', 'gpu_idle_before_ms', 'host_interval_ms'], 'rows': tl}
-    if lp.graphed:       # the captured iterations keep their scalars on the device: read the last ones once, after the timed region
-        ran, rd, rg = lp.outer()
-        finite = finite and all(np.isfinite(float(v)) for v in (rd['loss'], rd['acc_d'], rd['acc_g'], rg['loss'],
-                                                                 rg['feature_penalty'], rg['baseline']))
     ms = dt / args.steps * 1e3
     out = {
         'metric': 'audio-samples/sec per pass of the reference\'s training loop body (2 critic iterations + 1 generator iteration)',
@@ -302,7 +336,7 @@ def run_full(args, dev):
                     'kernel_table': [{'kernel': k, 'share': round(v['ms'] / dev_ms, 4), 'launches': v['n']}
                                      for k, v in sorted(prof.items(), key=lambda kv: -kv[1]['ms'])[:10]]})
     out.update({k: v for k, v in extra.items() if v is not None})
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline_full(min(args.cpu_batch, 8), 'rmsprop', min(32, os.cpu_count() or 1))
     print(json.dumps(out), flush=True)
     if status != 0 or not finite:
@@ -396,7 +430,15 @@ def main():
                          'stream beside the critic iteration; single-GPU graph only)')
     ap.add_argument('--no-graph', action='store_true',
                     help='enqueue every kernel from Python each step instead of replaying a hipGraph')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: the roofline objects (a profiled warm-up '
+                         'step and two eager steps), the replay check and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (both losses and every parameter it '
+                         'updated; --workload full: the last pass\'s results) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -455,10 +497,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- warm-up; the first warm-up step doubles as the discovery pass for the roofline kernel
+    # ---- warm-up; with --full the last warm-up step doubles as the discovery pass for the roofline kernel
     dominant, disc = None, None
     for i in range(max(args.warmup, 1)):
-        prof = (i == max(args.warmup, 1) - 1) and not args.no_roofline
+        prof = (i == max(args.warmup, 1) - 1) and args.full and not args.no_roofline
         if prof:
             torch.cuda.synchronize()
             K.Profiler.start(only=None)
@@ -510,11 +552,14 @@ def main():
     # sticky status word of the persistent recurrent launches: non-zero = some launch of the warm-up or the timed region
     # gave up waiting for its group (its results are NaN) - the number above would then be meaningless
     persist_status = K.lstm_persist_status(dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [('loss_d', losses['d']), ('loss_g', losses['g'])] +
+                     [('%s.%s' % (m, k), p_) for m, net in (('g', g), ('d', d)) for k, p_ in net.named_parameters()])
 
     # ---- replay check (outside the timed region): one more replay of the captured step against one EAGER step from
     # the same parameters / optimiser state on the same batch; loss_d and loss_g must agree
     replay = None
-    if graphed:
+    if graphed and args.full:
         from audiogan_amd import common
         nets = list(g.parameters()) + list(d.parameters())
         snap = [p_.detach().clone() for p_ in nets]
@@ -634,7 +679,7 @@ def main():
                  'tflops': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 2) if v['flops'] else None,
                  'alg_gbs': round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 1) if v['bytes'] else None}
                 for k, v in sorted(disc.items(), key=lambda kv: -kv[1]['ms'])[:14]]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # torch CPU does not scale past ~32 threads on this model (128 threads measured slower
             # than 8): use min(32, cores); `cores` in the result is the thread count actually used, `host_cores` what the box has
             out['cpu_baseline'] = cpu_baseline(args.cpu_batch if not alt else min(args.cpu_batch, 16),

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 out=gpurun_out/r04_extra_lines.json
 : > $out
-run() { echo "== $*" >&2; timeout -k 10 400 python bench.py "$@" --no-cpu-baseline 2> gpurun_out/extra_last.err | tail -1 >> $out || { echo "FAILED: $*" >&2; tail -5 gpurun_out/extra_last.err >&2; }; }
+run() { echo "== $*" >&2; timeout -k 10 400 python bench.py "$@" --full --no-cpu-baseline 2> "$out.err" | tail -1 >> $out || { echo "FAILED: $*" >&2; tail -5 "$out.err" >&2; }; }
 run --steps 20 --warmup 3
 run --steps 20 --warmup 3 --dtype bf16
 run --steps 20 --warmup 3 --dtype f32x3
