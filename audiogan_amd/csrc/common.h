@@ -156,3 +156,8 @@ int ag_conv_c1_try_bwdx(const ag_conv_args& a, int rb, hipStream_t st, int* rc);
 int ag_conv_c1_wgrad_slabs(int B, int A, int Lt, int s, int K, int* bper_out);
 int ag_conv_c1_wgrad(const float* dy, int64_t dy_bs, int64_t dy_cs, const float* x, int64_t x_bs, float* part, int B, int A,
                      int Lt, int Lx, int s, int K, int pad, int rb, hipStream_t st);
+// AG_CONV_C1=0 sends those shapes to the general kernels instead (read on every call: tests flip it in-process).
+inline bool ag_conv_c1_enabled() {
+  const char* e = getenv("AG_CONV_C1");
+  return !(e && e[0] == '0');
+}

@@ -62,7 +62,7 @@ extern "C" int ag_conv1d_engine(const ag_conv_args* args, void* stream) {
       p.n_cnt = n_hi - p.n_lo + 1;
     }
   }
-  if (getenv("AG_CONV_C1") == nullptr || getenv("AG_CONV_C1")[0] != '0') {
+  if (ag_conv_c1_enabled()) {
     // single-input-channel layers (D1, G1.conv) and their backward-data: streaming kernels (conv_c1.hip)
     int rc = AG_OK;
     if (ag_conv_c1_try_fwd(a, p.rb, (hipStream_t)stream, &rc)) return rc;
@@ -71,7 +71,7 @@ extern "C" int ag_conv1d_engine(const ag_conv_args* args, void* stream) {
   AG_REQUIRE(p.taps <= MAX_TAPS, "ag_conv1d_engine: more than %d taps", MAX_TAPS);
   p.sp_shift = ilog2_exact(p.sp);
   p.s_shift = ilog2_exact(a.stride);
-  p.efast = g_conv_efast && (int64_t)a.O * a.y_cs * 4 < ((int64_t)1 << 31) && (!a.res || (int64_t)a.O * a.res_cs * 4 < ((int64_t)1 << 31));
+  p.efast = (int64_t)a.O * a.y_cs * 4 < ((int64_t)1 << 31) && (!a.res || (int64_t)a.O * a.res_cs * 4 < ((int64_t)1 << 31));
   p.xvec = (((uintptr_t)a.x & 15) == 0) && (a.x_bs % 4 == 0) && (a.x_cs % 4 == 0);
   p.Cpad = ag_roundup(a.C, 2);
   p.Mpad = ag_roundup(p.Mrows, 32);
@@ -83,11 +83,9 @@ extern "C" int ag_conv1d_engine(const ag_conv_args* args, void* stream) {
   // Inside a replayed graph that second launch costs ~20 us of its own (a node never takes less than ~5, and each of its
   // workgroups stages a full weight panel for one column) while one more column of tiles costs 1 / (number of column
   // tiles) of the main launch: measured at batch 64, G2-G4.deconv forward 88 / 88 / 76 -> 81 / 81 / 68 us without the
-  // tail, G1.deconv (8 column tiles) 82 -> 84.  So: a tail only when the main launch has fewer than 8 column tiles
-  // (AG_CONV_TAIL=1: always, for A/B runs).
-  static const bool g_tail_always = [] { const char* e = getenv("AG_CONV_TAIL"); return e && e[0] == '1'; }();
+  // tail, G1.deconv (8 column tiles) 82 -> 84.  So: a tail only when the main launch has fewer than 8 column tiles.
   const int tail0 = p.n_cnt % 128;
-  const int tail = (g_tail_always || (p.n_cnt - tail0) / 128 < 8) ? tail0 : 0, main_cols = p.n_cnt - tail;
+  const int tail = (p.n_cnt - tail0) / 128 < 8 ? tail0 : 0, main_cols = p.n_cnt - tail;
   if (p.Mrows <= 64) {
     if (tail > 0 && tail <= 32 && main_cols > 0) {
       ConvP qm = p, qt = p;
@@ -105,14 +103,13 @@ extern "C" int ag_conv1d_engine(const ag_conv_args* args, void* stream) {
   // the same time after they all multiplied; twice as many half-width workgroups run in two rounds, and the second round's
   // staging and MFMAs overlap the first one's stores.  Measured (profiles/r04_conv_solo.txt, microseconds, 128 x 128 solo ->
   // 128 x 64): G1-G4.deconv forward 88 / 84 / 84 / 54 -> 78 (8-wave form) / 73 / 73 / 49 (solo); three tap slots (the strided
-  // convs' backward-data) lose 151 -> 165.  AG_CONV_HALF = 1 / 0 forces / forbids it (A/B runs).
-  static const int g_half = [] { const char* e = getenv("AG_CONV_HALF"); return e ? atoi(e) : -1; }();
+  // convs' backward-data) lose 151 -> 165.
   // (fp32 kernels only: the bf16-MFMA kernel's launches are 40-60 us of mostly stores and lose with half tiles, 51 -> 59 us)
-  if (a.mode == 1 && (g_half == 1 || (g_half != 0 && p.taps == 2 && !p.rb))) return ag_conv_cfg_2122(p, st);
+  if (a.mode == 1 && p.taps == 2 && !p.rb) return ag_conv_cfg_2122(p, st);
   // fewer than two 128x128 workgroups per CU: one MFMA wave per SIMD cannot keep the matrix pipe fed, take
   // half-width tiles (twice the workgroups, two co-resident per CU)
   // (the bf16 kernel runs one workgroup per CU and wants the full tile's reuse of the staged weights)
-  const bool bfp = p.rb && ag_cdiv(p.Cpad, 16) * p.taps >= 32 && g_conv_bf16_mfma;      // (the deep-reduction variant)
+  const bool bfp = p.rb && ag_cdiv(p.Cpad, 16) * p.taps >= 32;      // (the deep-reduction variant)
   if (!bfp && (int64_t)ag_cdiv(p.n_cnt, 128) * ag_cdiv(p.Mrows, 128) * a.B < 512) return ag_conv_cfg_2122(p, st);
   if (tail > 0 && tail <= 32 && main_cols > 0) {
     ConvP qm = p, qt = p;

@@ -833,20 +833,11 @@ static inline int ilog2_exact(int v) {
   return -1;
 }
 
-// fp32 layout + its bf16 image (common.h ag_wq_*)
-static const bool g_conv_efast = [] { const char* e = getenv("AG_CONV_EFAST"); return !(e && e[0] == '0'); }();
-static const bool g_conv_pipe = [] { const char* e = getenv("AG_CONV_PIPE"); return !(e && e[0] == '0'); }();
-// AG_CONV_BF16_MFMA=0 keeps the fp32-MFMA rounding emulation in bf16 mode (A/B measurements)
-static const bool g_conv_bf16_mfma = [] { const char* e = getenv("AG_CONV_BF16_MFMA"); return !(e && e[0] == '0'); }();
-
-// AG_CONV_SOLO: -1 (default) = by the heuristic of launch_cfg, 0 = never, 1 = every 128 x 128-tile fp32 launch; AG_CONV_SOLO_K:
-// largest reduction length C * taps that takes the solo form under the heuristic.  Measured at batch 64 (tools/prof_layers.py,
+// Largest reduction length C * taps that takes the solo form (launch_cfg).  Measured at batch 64 (tools/prof_layers.py,
 // profiles/r04_conv_solo.txt; 8-wave form -> solo -> solo + DMA staging, microseconds): the generator's transposed convs forward
 // 92/88/86/72 -> 87/81/80/63 -> 88/83/84/55, its strided convs' backward-data 89/162/172 -> 83/150/139 (DMA: the same); a
 // strided conv itself (mode 0, G1.deconv backward-data) LOSES 56 -> 68, so the form is taken for mode 1 only.
-static const int g_conv_solo = [] { const char* e = getenv("AG_CONV_SOLO"); return e ? atoi(e) : -1; }();
-static const int g_conv_solo_k = [] { const char* e = getenv("AG_CONV_SOLO_K"); return e ? atoi(e) : 512; }();
-static const bool g_conv_dma = [] { const char* e = getenv("AG_CONV_DMA"); return !(e && e[0] == '0'); }();
+constexpr int CONV_SOLO_K = 512;
 
 template <int TO, int TTL, int WO, int WT, int TAPS, int S0>
 static int launch_one(ConvP& p, size_t lds, dim3 grid, hipStream_t st) {
@@ -911,7 +902,7 @@ static int launch_bf16(ConvP& p, hipStream_t st) {
 template <int TO, int TTL, int WO, int WT>
 static int launch_cfg(ConvP& p, hipStream_t st) {
   constexpr int OT = 32 * TO * WO, TT = 32 * TTL * WT;
-  if (p.rb && p.a.C >= 16 && g_conv_bf16_mfma) {
+  if (p.rb && p.a.C >= 16) {
     const int rc = launch_bf16<TO, TTL, WO, WT>(p, st);
     if (rc != -1) return rc;
   }
@@ -941,7 +932,7 @@ static int launch_cfg(ConvP& p, hipStream_t st) {
   // fit 31 bits.  The chunk is trimmed to that round.
   p.pipe = 0;
   if (p.xvec && a.Lin % 4 == 0 && a.Lin >= 4 && (int64_t)a.C * a.x_cs * 4 < ((int64_t)1 << 31) &&
-      (int64_t)p.Cpad * p.taps * p.Mpad * 4 < ((int64_t)1 << 31) && g_conv_pipe) {
+      (int64_t)p.Cpad * p.taps * p.Mpad * 4 < ((int64_t)1 << 31)) {
     const int nq = (p.sp * p.ncols + 6) / 4 + 1;
     int cf = cc;
     constexpr int FXH = OT <= 32 ? 7 : 4, FWH = OT <= 32 ? 3 : 8;   // = the kernel's FX, FW
@@ -952,18 +943,17 @@ static int launch_cfg(ConvP& p, hipStream_t st) {
       p.pipe = 1;
     }
   }
-  // solo form (see the kernel): AG_CONV_SOLO = 1 forces it for every 128 x 128-tile launch, 0 forbids it (A/B runs);
-  // AG_CONV_DMA = 0 keeps its staging on the register path
+  // solo form (see the kernel and CONV_SOLO_K)
   p.solo = 0;
   p.dma = 0;
   size_t per_cs = per_c;
-  if (OT == 128 && (TT == 128 || TT == 64) && g_conv_solo != 0) {
+  if (OT == 128 && (TT == 128 || TT == 64)) {
     const int ktot = p.Cpad * p.taps;
     // (half-width tiles: the solo form wins up to C * taps = 128, the 8-wave form above - G1.deconv forward 78 vs 88 us)
-    if (g_conv_solo == 1 || (a.mode == 1 && ktot <= (TT == 64 ? g_conv_solo_k / 4 : g_conv_solo_k))) {
+    if (a.mode == 1 && ktot <= (TT == 64 ? CONV_SOLO_K / 4 : CONV_SOLO_K)) {
       p.solo = 1;
       p.pipe = 0;
-      if (a.mode == 1 && !p.rb && g_conv_dma && p.xvec && a.Lin % 4 == 0 && p.Cpad % 16 == 0 && p.Mpad % 4 == 0 &&
+      if (!p.rb && p.xvec && a.Lin % 4 == 0 && p.Cpad % 16 == 0 && p.Mpad % 4 == 0 &&
           (((uintptr_t)a.wp) & 15) == 0) {
         // DMA staging: row pitch a multiple of 16 floats that covers the window from floor4(base) on
         p.dma = 1;

@@ -494,9 +494,6 @@ static int wgrad_slices(int A, int CK, int AT, int NT, int total) {
   return gz;
 }
 
-// AG_CONV_BF16_MFMA=0 keeps the fp32-MFMA rounding emulation in bf16 mode (A/B measurements)
-static const bool g_wgrad_bf16_mfma = [] { const char* e = getenv("AG_CONV_BF16_MFMA"); return !(e && e[0] == '0'); }();
-
 // bf16-MFMA variant; -1 = the shape does not fit its staging scheme (caller takes the fp32 kernel)
 template <int TA, int TN, int WA, int WN>
 static int launch_wgrad_bf16(WgP& p, hipStream_t st, AgWs ws) {
@@ -534,7 +531,7 @@ static int launch_wgrad_bf16(WgP& p, hipStream_t st, AgWs ws) {
 template <int TA, int TN, int WA, int WN>
 static int launch_wgrad(WgP& p, hipStream_t st, AgWs ws) {
   constexpr int AT = 32 * TA * WA, NT = 32 * TN * WN;
-  if (p.rb && g_wgrad_bf16_mfma) {
+  if (p.rb) {
     const int rc = launch_wgrad_bf16<TA, TN, WA, WN>(p, st, ws);
     if (rc != -1) return rc;
   }
@@ -641,7 +638,7 @@ extern "C" int ag_conv1d_wgrad(const float* sh, int64_t sh_bs, int64_t sh_cs, co
   if (C == 1 && ws.p && ag_conv_c1_wgrad_slabs(B, A, Lsh, stride, K, nullptr) > 0 &&
       (((uintptr_t)sh & 15) == 0) && sh_bs % 4 == 0 && sh_cs % 4 == 0 &&
       ws.numel >= (int64_t)ag_conv_c1_wgrad_slabs(B, A, Lsh, stride, K, nullptr) * A * K &&
-      (getenv("AG_CONV_C1") == nullptr || getenv("AG_CONV_C1")[0] != '0')) {
+      ag_conv_c1_enabled()) {
     // D1 / G1.conv: streaming kernel, one partial [A][K] per block, fixed-order second stage (conv_c1.hip)
     const int slabs = ag_conv_c1_wgrad_slabs(B, A, Lsh, stride, K, nullptr);
     const int rc = ag_conv_c1_wgrad(sh, sh_bs, sh_cs, lg, lg_bs, ws.p, B, A, Lsh, Llg, stride, K, pad, p.rb, st);

@@ -562,10 +562,7 @@ int ag_splitk_reduce(const float* part, int Z, int64_t pitch, int M, int N, floa
 // Tile shape of the LDS-DMA kernel (gemm_tile.h) for an [M x N] output in `ksplit` K slices.  A CU's matrix pipes are shared
 // by the workgroups resident on it, so a launch takes about ceil(workgroups / 256) x (BM x BN) / rate(shape): prefer the
 // largest tile that still gives every CU a workgroup.  Rates: TF measured by tools/gemm_lab.hip (profiles/r04_gemm_lab.txt).
-// AG_GEMM_TILE=0..3 in the environment forces a shape (A/B switch of tools/prof_gemm.py).
-static const int g_gemm_tile_force = [] { const char* e = getenv("AG_GEMM_TILE"); return e ? atoi(e) : -1; }();
 static int gemm_pick_tile(int M, int N, int ksplit) {
-  if (g_gemm_tile_force >= 0 && g_gemm_tile_force <= 3) return g_gemm_tile_force;
   static const int order[4] = {3, 1, 2, 0};
   static const double rate[4] = {120., 133., 133., 137.};
   int best = 0;
@@ -669,9 +666,8 @@ extern "C" int ag_gemm(const float* A, int lda, int ta, const float* B, int ldb,
     rc = launch_gemm_bf16(p, ta, tb, st, x3);
   } else if (use128) {
     // LDS-DMA variant: whole 16-k tiles only, 16-byte aligned rows, row-contiguous operands with rows % 4 == 0
-    // (AG_GEMM_NODMA=1 in the environment forces the register-staged kernel: A/B switch for tools/prof_gemm.py)
     const bool dma = p.vecA && p.vecB && K % 16 == 0 && p.kchunk % 16 == 0 && (ta == 0 || M % 4 == 0) &&
-                     (tb == 1 || N % 4 == 0) && M >= 4 && N >= 4 && !p.rb && getenv("AG_GEMM_NODMA") == nullptr;
+                     (tb == 1 || N % 4 == 0) && M >= 4 && N >= 4 && !p.rb;
     rc = dma ? launch_gemm_dma(p, ta, tb, st) : launch_gemm<2, 2, 2, 2>(p, ta, tb, st);  // 128x128
   } else {
     rc = launch_gemm<1, 1, 2, 2>(p, ta, tb, st);              // 64x64

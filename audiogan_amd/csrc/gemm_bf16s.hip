@@ -8,8 +8,9 @@
 //
 //   C[M,N] (fp32 and / or bf16) = act(alpha * op(A) op(B) + beta * C + bias + res)
 //
-// 128 x 128 tile, BK = 64, 4 waves x (2 x 2) v_mfma_f32_32x32x16_bf16, two LDS buffers of 32 KiB, the DMA of tile i+1 in
-// flight under the MFMAs of tile i.  Two operand images, chosen per operand by how it is stored:
+// 128 x 128 tile, BK = 64, 4 waves x (2 x 2) v_mfma_f32_32x32x16_bf16, ONE LDS stage of 32 KiB (the two operand images)
+// and registers capped for 4 waves per SIMD: four workgroups per CU hide each other's DMA latency.  Two operand images,
+// chosen per operand by how it is stored:
 //   KC  k contiguous ([rows][K]: activations x weights^T):  image [128 rows][64 k], 128-byte rows; 16-byte chunk c of row
 //       r sits in slot c ^ ((r >> 1) & 7); one ds_read_b128 per MFMA operand (the image of gemm_bf16_kernel).
 //   KS  k strided ([K][rows]: both operands of a weight gradient dW = dY^T X, the weight of a data gradient dX = dY W):
@@ -18,21 +19,48 @@
 //       16-lane group reads a 4 k x 16 rows block and each lane receives one row's 4 k).
 // LDS-DMA writes LDS in lane order, so both swizzles are applied to the SOURCE address of a DMA lane and to the reader.
 // Needs K (and a K slice) % 64 == 0, 16-byte aligned rows, and row counts % 8 == 0 for KS operands.
+//
+// The staging form was chosen over the critic's 11 product shapes (tools/prof_gemm_h.py, sum of the launch times; the
+// alternatives were measured with an A/B switch since removed): this one 686 us, the same with the registers uncapped (3
+// workgroups per CU) 807; BK 64 with two stages (64 KiB, 2 per CU, the DMA of tile i+1 under the MFMAs of tile i - 16 MFMAs
+// of 32 cycles do not cover an HBM round trip) 830; BK 32 with two stages (32 KiB, 4 per CU) 764, uncapped 859; the
+// fp32-operand bf16 kernel 885.  Larger tiles did not win either: DESIGN.md section 4.3.
 #include "common.h"
-// (GemmH, the image swizzles - and the larger-tile kernel that tools/gemm_lab_h.hip measured and that did NOT beat this one
-// on the critic's shapes: see the table in the header)
-#define AG_GEMMH_TILE_CASES(F)
-#include "gemm_bf16_tile.h"
 
-// BK: k per stage (64 or 32);  NBUF: LDS stages (2: the DMA of tile i+1 under the MFMAs of tile i;  1: one stage, 32 KiB (BK
-// 64) per workgroup - latency is hidden by co-resident workgroups instead, four per CU)
-template <int TA, int TB, int BK, int NBUF, int WPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void gemm_bf16s_kernel(const GemmH p) {
-  constexpr int BM = 128, BN = 128, IMG = 128 * BK * 2;            // bytes per operand image (either form)
+typedef short hbf16x8 __attribute__((ext_vector_type(8)));
+typedef short hs16x4 __attribute__((ext_vector_type(4)));
+
+#define H_LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
+#define H_GLB_AS(p) ((const __attribute__((address_space(1))) void*)(p))
+
+struct GemmH {
+  const unsigned short* A;      // TA = 0: [M][K] (lda)   TA = 1: [K][M] (lda)
+  const unsigned short* B;      // TB = 1: [N][K] (ldb)   TB = 0: [K][N] (ldb)
+  float* C;                     // fp32 output (ldc) or NULL
+  unsigned short* C16;          // bf16 output (ldc16) or NULL
+  const float* bias;            // [N] fp32
+  const float* res;             // fp32 residual / gate source (ldres) or NULL
+  const unsigned short* res16;  // bf16 residual / gate source (ldres16) or NULL
+  const unsigned short* gate16; // bf16 SAVED OUTPUT of a LeakyReLU (ldgate16) or NULL: the result (after bias / res) is scaled by
+                                // that activation's derivative - a residual layer's backward (W^T da + da) gated by the layer below
+  float* part;                  // split-K slabs
+  int lda, ldb, ldc, ldc16, ldres, ldres16, ldgate16;
+  int M, N, K, ksplit, kchunk, act;
+  float alpha, beta, slope;
+};
+
+// KC image, rows of 128 bytes: chunk c of row r in slot c ^ ((r >> 1) & 7)
+__device__ __forceinline__ int h_kc_slot(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+__device__ __forceinline__ int h_ks_f(int k) { return ((k & 3) << 2) | ((k >> 2) & 3); }
+__device__ __forceinline__ float h_bf(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
+
+template <int TA, int TB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_bf16s_kernel(const GemmH p) {
+  constexpr int BM = 128, BN = 128, BK = 64, IMG = 128 * BK * 2;   // IMG: bytes per operand image (either form)
   constexpr int NCH = IMG / 16 / 256;                               // 16-byte chunks per thread, operand and stage
   constexpr int KCC = BK / 8;                                       // chunks per row of the KC image
   constexpr bool AKS = TA == 1, BKS = TB == 0;
-  extern __shared__ __attribute__((aligned(16))) char sm[];        // NBUF x (A image + B image)
+  extern __shared__ __attribute__((aligned(16))) char sm[];        // A image + B image
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int wm0 = (wid >> 1) * 64, wn0 = (wid & 1) * 64;
@@ -56,14 +84,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   for (int it = 0; it < NCH; ++it) {
     const int j = tid + 256 * it;
     if (!AKS) {
-      const int r = j / KCC, c = (j % KCC) ^ (BK == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3));
+      const int r = j / KCC, c = (j % KCC) ^ ((r >> 1) & 7);
       asrc[it] = p.A + (int64_t)min(m0 + r, p.M - 1) * p.lda + 8 * c;
     } else {
       const int k = j >> 4, ch = (j & 15) ^ h_ks_f(k);
       asrc[it] = p.A + (int64_t)k * p.lda + min(m0 + 8 * ch, p.M - 8);
     }
     if (!BKS) {
-      const int r = j / KCC, c = (j % KCC) ^ (BK == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3));
+      const int r = j / KCC, c = (j % KCC) ^ ((r >> 1) & 7);
       bsrc[it] = p.B + (int64_t)min(n0 + r, p.N - 1) * p.ldb + 8 * c;
     } else {
       const int k = j >> 4, ch = (j & 15) ^ h_ks_f(k);
@@ -72,8 +100,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   }
   const int64_t astep = AKS ? (int64_t)p.lda : 1, bstep = BKS ? (int64_t)p.ldb : 1;     // elements per unit of k
 
-  auto stage = [&](int k0, int buf) {
-    char* As = sm + buf * 2 * IMG;
+  auto stage = [&](int k0) {
+    char* As = sm;
     char* Bs = As + IMG;
 #pragma unroll
     for (int it = 0; it < NCH; ++it) {
@@ -101,7 +129,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if (!AKS) {
-          av[i] = *reinterpret_cast<const hbf16x8*>(As + h_kc_slot<BK>(wm0 + 32 * i + l31, 2 * s_ + h));
+          av[i] = *reinterpret_cast<const hbf16x8*>(As + h_kc_slot(wm0 + 32 * i + l31, 2 * s_ + h));
         } else {
           hs16x4 v4[2];
 #pragma unroll
@@ -116,7 +144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (!BKS) {
-          bv[j] = *reinterpret_cast<const hbf16x8*>(Bs + h_kc_slot<BK>(wn0 + 32 * j + l31, 2 * s_ + h));
+          bv[j] = *reinterpret_cast<const hbf16x8*>(Bs + h_kc_slot(wn0 + 32 * j + l31, 2 * s_ + h));
         } else {
           hs16x4 v4[2];
 #pragma unroll
@@ -138,26 +166,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 
   const int kbeg = bz * p.kchunk;
   const int kend = (kbeg + p.kchunk < p.K) ? kbeg + p.kchunk : p.K;
-  if (NBUF == 2) {
-    stage(kbeg, 0);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-      if (k0 + BK < kend) stage(k0 + BK, buf ^ 1);
-      mfma_tile(sm + buf * 2 * IMG, sm + buf * 2 * IMG + IMG);
-      // (keeps the barrier - and its vmcnt(0) on the next tile's DMA - behind ALL of this tile's MFMAs)
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-      buf ^= 1;
-    }
-  } else {
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-      stage(k0, 0);
-      __syncthreads();                    // vmcnt(0) + barrier: the tile is in LDS
-      mfma_tile(sm, sm + IMG);
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();                    // every wave is done reading before the next tile overwrites it
-    }
+  for (int k0 = kbeg; k0 < kend; k0 += BK) {
+    stage(k0);
+    __syncthreads();                    // vmcnt(0) + barrier: the tile is in LDS
+    mfma_tile(sm, sm + IMG);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();                    // every wave is done reading before the next tile overwrites it
   }
 
   // ---- epilogue.  Full tiles with 16-byte aligned outputs go through LDS: the accumulators (column per lane) are written as a
@@ -261,30 +275,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     }
 }
 
-// variant of the staging structure (AG_GEMMH_VARIANT, for A/B runs): 1 (default) = BK 64, ONE stage (32 KiB) and registers
-// capped at 128: four workgroups per CU hide each other's DMA latency;  0 = BK 64, two stages (64 KiB: 2 workgroups per CU,
-// the DMA of tile i+1 under the MFMAs of tile i - 16 MFMAs of 32 cycles do not cover an HBM round trip);  2 = BK 32, two
-// stages (32 KiB), 4 per CU;  3 / 4 = as 1 / 2 with the registers uncapped (3 per CU).
-// Measured over the critic's 11 product shapes (tools/prof_gemm_h.py, sum of the launch times): 0: 830 us, 1: 686, 2: 764,
-// 3: 807, 4: 859 (the fp32-operand bf16 kernel: 885).
-static const int g_h_variant = [] { const char* e = getenv("AG_GEMMH_VARIANT"); return e ? atoi(e) : 1; }();
-
-template <int TA, int TB, int BK, int NBUF, int WPE>
-static void launch_h2(const GemmH& p, dim3 grid, hipStream_t st) {
-  auto kern = gemm_bf16s_kernel<TA, TB, BK, NBUF, WPE>;
-  const int stage_bytes = NBUF * 2 * 128 * BK * 2;
-  const int lds = stage_bytes < 32 * 1024 ? 32 * 1024 : stage_bytes;       // (the epilogue's [64][128] fp32 image)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
-}
-
 template <int TA, int TB>
 static void launch_h(const GemmH& p, dim3 grid, hipStream_t st) {
-  if (g_h_variant == 1) launch_h2<TA, TB, 64, 1, 4>(p, grid, st);
-  else if (g_h_variant == 2) launch_h2<TA, TB, 32, 2, 4>(p, grid, st);
-  else if (g_h_variant == 3) launch_h2<TA, TB, 64, 1, 3>(p, grid, st);
-  else if (g_h_variant == 4) launch_h2<TA, TB, 32, 2, 3>(p, grid, st);
-  else launch_h2<TA, TB, 64, 2, 2>(p, grid, st);
+  auto kern = gemm_bf16s_kernel<TA, TB>;
+  const int lds = 32 * 1024;          // one stage (2 x 128 x 64 bf16) = the epilogue's [64][128] fp32 image
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
 }
 
 static int h_pick_ksplit(int64_t tiles, int64_t mn, int K) {

@@ -73,9 +73,7 @@ __device__ __forceinline__ void xcd_place(int& bx, int& by, int& bz) {
 
 // TA / TB: 0 = A stored [M][K] / B stored [K][N], 1 = A stored [K][M] / B stored [N][K]   (as ag_gemm's ta / tb)
 // BM x BN: workgroup tile; TI x TJ: blocks of 32 x 32 per wave.  Dynamic LDS: 2 stages x (BM + BN) x 16 floats.
-// DBG: ablations of tools/gemm_lab.hip (LAB_DBG) - 1 = the lab's 1-D tile placement, 2 = plain-store epilogue; the library
-// instantiates DBG = 0 only.
-template <int TA, int TB, int BM, int BN, int TI, int TJ, int DBG = 0>
+template <int TA, int TB, int BM, int BN, int TI, int TJ>
 __global__ __launch_bounds__((BM / (32 * TI)) * (BN / (32 * TJ)) * 64, (BM * BN >= 65536 ? 2 : 4))      // (threads, waves per SIMD)
 void gemm_tile_kernel(const GemmP p) {
   constexpr int WJ = BN / (32 * TJ), NW = (BM / (32 * TI)) * WJ;
@@ -88,14 +86,7 @@ void gemm_tile_kernel(const GemmP p) {
   const int l31 = lane & 31, h = lane >> 5;
   const int wm0 = (wid / WJ) * 32 * TI, wn0 = (wid % WJ) * 32 * TJ;
   int bx, by, bz;
-  if (DBG & 1) {
-    const int nb = gridDim.x * gridDim.y;
-    int id = blockIdx.y * gridDim.x + blockIdx.x;
-    id = (id & 7) * (nb >> 3) + (id >> 3);
-    by = id / gridDim.x; bx = id - by * gridDim.x; bz = 0;
-  } else {
-    xcd_place(bx, by, bz);
-  }
+  xcd_place(bx, by, bz);
   const int m0 = by * BM, n0 = bx * BN;
 
   // this wave's DMA instructions: source at k = 0 of the operand, k step, wave-uniform LDS offset in the stage
@@ -180,18 +171,6 @@ void gemm_tile_kernel(const GemmP p) {
     buf ^= 1;
   }
 
-  if (DBG & 2) {
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-        float* dst = p.C + (int64_t)row * p.ldc + n0 + wn0 + l31;
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) dst[32 * j] = acc[i][j][e];
-      }
-    return;
-  }
   if (p.ksplit > 1 && m0 + BM <= p.M && n0 + BN <= p.N) {
     // interior tile of a K slice: the partial tile goes to its slab as it is (alpha applied), no tests per element
     float* slab = p.part + (int64_t)bz * p.M * p.N;
@@ -210,7 +189,7 @@ void gemm_tile_kernel(const GemmP p) {
   if (p.ksplit == 1 && m0 + BM <= p.M && n0 + BN <= p.N) {
     // interior tile: no bounds tests.  The options are uniform: the reads of `res` / of C (beta) are issued EG rows at a time
     // (all in flight together) under one branch each, the activation is chosen once around the arithmetic + stores - an
-    // epilogue that tested the options per element cost 7 % of a 256 x 256 tile's time (tools/gemm_lab.hip, LAB_DBG).
+    // epilogue that tested the options per element cost 7 % of a 256 x 256 tile's time (measured in tools/gemm_lab.hip with an ablation since removed).
     const bool hb = p.bias != nullptr, hr = p.res != nullptr, hbeta = p.beta != 0.f;
     constexpr int EG = 4;                        // rows per group: EG x TJ values of res and of C in registers
     float bj[TJ];

@@ -88,9 +88,6 @@ def _mat(t, name):
 # ------------------------------------------------------------------------------------
 import os as _os0
 
-if _os0.environ.get('AG_DETERMINISTIC', '1') == '0':
-    raise ImportError('audiogan_amd: AG_DETERMINISTIC=0 asked for the float-atomic reductions of round 1; they were removed '
-                      '(round 4) - every cross-workgroup sum is two-stage and bitwise reproducible.  Unset the variable.')
 _SMALL_WS = 1 << 17        # floats; enough for the bias / channel / column sums at every BASELINE size
 
 
@@ -901,7 +898,7 @@ def _work_gemm(A, B, Cm, ta=False, tb=False, *a_, **kw):
             t = _cdiv(wgs, 256) * bm * bn / rate + 1e-9 * wgs * bm * bn
             if best is None or t < best_t * 0.98:
                 best, best_t = (bm, bn, ti, tj), t
-        key = 'gemm_tile_kernel<%d,%d,%d,%d,%d,%d,0>' % ((int(ta), int(tb)) + best)
+        key = 'gemm_tile_kernel<%d,%d,%d,%d,%d,%d>' % ((int(ta), int(tb)) + best)
     else:
         key = 'gemm_kernel<%s,%d,%d>' % ('2,2,2,2' if use128 else '1,1,2,2', int(ta), int(tb))
     return key, 2.0 * M * N * Kd, 4.0 * (M * Kd + N * Kd + M * N)
@@ -920,8 +917,7 @@ def _work_conv(x, wp, y, K_, stride, pad, mode, *a_, **kw):
         tile = '2,1,2,2'
     else:
         tile = '2,2,2,2'
-    if mode == 1 and _cdiv(K_, stride) == 2 and rows > 64 and lib.ag_get_precision() != 1 and \
-            _os0.environ.get('AG_CONV_HALF', '-1') != '0':
+    if mode == 1 and _cdiv(K_, stride) == 2 and rows > 64 and lib.ag_get_precision() != 1:
         tile = '2,1,2,2'         # (conv_engine.hip: two tap slots take 128 x 64 tiles)
     macs = B * O * Lout * Cc * K_ if mode == 0 else B * Cc * Lin * O * K_
     if (K_, stride) == (7, 2) and _os0.environ.get('AG_CONV_C1', '1') != '0':

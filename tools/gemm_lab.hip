@@ -231,31 +231,6 @@ static void run_lib(int ta, int tb, int shape, int ksplit = 1) {
   fflush(stdout);
 }
 
-template <int DBG>
-static void run_dbg() {
-  GemmP q;
-  q.A = dA; q.B = dB; q.C = dC; q.bias = nullptr; q.res = nullptr;
-  q.lda = gp.K; q.ldb = gp.K; q.ldc = gp.N; q.ldres = 0;
-  q.M = gp.M; q.N = gp.N; q.K = gp.K; q.alpha = 1.f; q.beta = 0.f; q.slope = 0.f; q.act = 0; q.vecA = q.vecB = 1; q.rb = 0;
-  q.ksplit = 1; q.kchunk = gp.K; q.part = nullptr;
-  auto k = gemm_tile_kernel<0, 1, 256, 256, 2, 4, DBG>;
-  const int lds = 2 * 512 * 16 * 4;
-  CK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  dim3 grid(gp.N / 256, gp.M / 256, 1);
-  for (int rep = 0; rep < 2; ++rep) {
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k, grid, dim3(512), lds, 0, q);
-    CK(hipDeviceSynchronize());
-    CK(hipEventRecord(e0, 0));
-    for (int i = 0; i < 20; ++i) hipLaunchKernelGGL(k, grid, dim3(512), lds, 0, q);
-    CK(hipEventRecord(e1, 0));
-    CK(hipEventSynchronize(e1));
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    printf("dbg %d (1 = lab placement, 2 = plain epilogue): %8.1f us %7.1f TF\n", DBG, ms * 50, 2.0 * gp.M * gp.N * gp.K / (ms * 50e-6) / 1e12);
-  }
-  fflush(stdout);
-}
-
 int main(int argc, char** argv) {
   gp.M = argc > 3 ? atoi(argv[1]) : 16384; gp.N = argc > 3 ? atoi(argv[2]) : 1024; gp.K = argc > 3 ? atoi(argv[3]) : 1024;
   gp.lda = gp.K; gp.ldb = gp.K; gp.ldc = gp.N;
@@ -305,17 +280,8 @@ int main(int argc, char** argv) {
   }
   run<128, 128, 2, 2, 2, 0>("V128x128/2x2/s2", true);
   run<128, 128, 2, 2, 2, 0>("V128x128/2x2/s2");
-  if (!getenv("LAB_DBG")) {
-    for (int shape = 0; shape < 4; ++shape)
-      for (int lay = 0; lay < 4; ++lay) run_lib(lay >> 1, lay & 1, shape);
-  }
-  if (getenv("LAB_DBG")) {
-    run<256, 256, 2, 4, 2, 0>("V256x256/2x4/s2 (8 waves)");
-    run_dbg<0>(); run_dbg<1>(); run_dbg<2>(); run_dbg<3>();
-    run<256, 256, 2, 4, 2, 0>("V256x256/2x4/s2 (8 waves)");
-    run_dbg<0>(); run_dbg<3>();
-    return 0;
-  }
+  for (int shape = 0; shape < 4; ++shape)
+    for (int lay = 0; lay < 4; ++lay) run_lib(lay >> 1, lay & 1, shape);
   if (getenv("LAB_LIB_ONLY")) return 0;
   run<128, 128, 2, 2, 2, 1>("V128x128/2x2/s2/noDMA");
   run<128, 128, 2, 2, 2, 2>("V128x128/2x2/s2/noStore");

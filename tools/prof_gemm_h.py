@@ -1,6 +1,5 @@
 """micro-driver: the critic's GEMM shapes on bf16-STORED operands (ag_gemm_h) next to the fp32-operand bf16 kernel (ag_gemm in
-'bf16' precision mode), microseconds and TFLOP/s per shape.  AG_GEMMH_VARIANT selects the staging structure (gemm_bf16s.hip)."""
-import os
+'bf16' precision mode), microseconds and TFLOP/s per shape."""
 import sys
 import torch
 sys.path.insert(0, '.')
@@ -9,7 +8,6 @@ K.set_precision('bf16')
 shapes = [(16384, 2048, 512, 0, 1), (16384, 1024, 1024, 0, 1), (16384, 512, 1024, 0, 1), (8192, 2048, 512, 0, 1),
           (16384, 512, 4096, 0, 0), (16384, 1024, 1024, 0, 0), (16384, 1024, 512, 0, 0),
           (2048, 512, 16384, 1, 0), (1024, 1024, 16384, 1, 0), (512, 1024, 16384, 1, 0), (2048, 512, 8192, 1, 0)]
-print('variant', os.environ.get('AG_GEMMH_VARIANT', '0'))
 tot_h = tot_f = 0.0
 for M, N, Kd, ta, tb in shapes:
     A = torch.randn((Kd, M) if ta else (M, Kd), device='cuda')
