@@ -109,6 +109,8 @@ SIGNATURES = {
     'ag_grufront_bwd_persist': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, C.c_int, vp, vp, vp, vp, vp, i64] + [C.c_int] * 5 + [vp]),
     'ag_gfront_fwd_persist': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64] + [C.c_int] * 5 + [vp]),
     'ag_grufront_fwd_persist': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64] + [C.c_int] * 5 + [vp]),
+    'ag_gfront_gen_persist': (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]
+                              + [C.c_int] * 5 + [vp]),
     'ag_build_zc': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'ag_critic_batch': (C.c_int, [vp, i64, vp, i64, C.c_int, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp,
                                   C.POINTER(i32), C.c_int, vp, vp, vp, C.c_int, vp, vp]),
@@ -146,7 +148,7 @@ def _load():
     return lib
 
 
-ABI_VERSION = 10      # what this package was written against (csrc/api.hip: ag_abi_version)
+ABI_VERSION = 11      # what this package was written against (csrc/api.hip: ag_abi_version)
 
 lib = _load()
 if lib.ag_abi_version() != ABI_VERSION:

@@ -24,6 +24,8 @@
 // in flight per device (all its workgroups must be co-resident).
 #include "common.h"
 
+#include <type_traits>
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Workspace layout: [sticky area PS_STICKY_BYTES][header PS_HDR_BYTES][exchange buffers].
@@ -693,14 +695,39 @@ struct FrontFwdP {
   int T, B, ldwx, nrt, rb;
 };
 
+// Generation mode (GEN = 1, ag_gfront_gen_persist): sampling, no autograd.  No history is written (gates, hs, cs, gh, xt:
+// only x); `gates` holds the pre-activations and is only read.  Per frame the projection workgroups of column tile 0 (ut = 0
+// and 1: one per 16-clip subtile) also form the stop logit s = h_t . w_s + b_s beside their MFMA tile and draw the stop,
+// stop = u[t,b] < sigmoid(s).  Exit rule: every subtile publishes, before its x flag of frame t,
+//   gen_all[sub]  (write-once) = t + 1 at the first frame t by which every clip of the subtile has drawn a stop
+//   gen_done[sub] = t + 1: the subtile's decisions of frames <= t are final
+// At the top of frame t + 1 every workgroup waits for gen_done >= t - GEN_LAG + 1 of ALL subtiles and leaves the loop iff every
+// gen_all is in [1, t - GEN_LAG + 1].  Both are final, write-once facts about frame t - GEN_LAG, so every workgroup takes
+// the same decision at the same frame and nobody waits for a flag that is never published.  The lag keeps the wait off the
+// critical path: the h part of frame t + 1 may start before phase B of frame t has finished anywhere; the GEN_LAG frames run
+// past the last stop are correct frames that the caller discards.
+#define PS_GEN_OFF (PS_FLAG_OFF + 512)     // header words of the generation mode (the fronts' flags use at most 320)
+#define GEN_LAG 1
+
+struct FrontGenP : FrontFwdP {
+  const float* ws;     // stop head: materialised weight [S], bias [1]
+  const float* bs;
+  const float* u;      // [T,B] uniforms
+  float* s;            // [B,T] out, row pitch lds: stop logits of the frames run
+  int64_t lds;
+  int* first;          // [B] out: frames generated per clip (1 + first stop frame, T if none)
+  int* t_run;          // [1] out: frames run
+};
+
 // PM: 0 = as stored / operands rounded in registers when p.rb (fp32 MFMA); 2 = AG_PREC_BF16 on the bf16 MFMAs (panels
 // in registers as bf16: 8 k per 4 VGPRs)
 // CELL: 0 = LSTMCell (4 gate columns per unit: i f g o).  1 = GRU cell (BASELINE configs[3]; PM = 0 only): the 4 column
 // blocks of a unit tile are  r | z | n_h | n_x : the h panel carries W_hr, W_hz, W_hn and zeros, the x panel W_xr, W_xz,
 // zeros and W_xn, so that ONE accumulator ends up with  r, z pre-activations complete and the two halves of n apart
 // (n = tanh(n_x + r * (n_h + b_hn)));  h_t = (1 - z) n + z h_{t-1} stays in a register like the LSTM's cell state.
-template <int S, int FS, int PM, int CELL = 0>
-__global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP p) {
+// GEN: 1 = generation mode (FrontGenP, see above); 0 = the training forward.
+template <int S, int FS, int PM, int CELL = 0, int GEN = 0>
+__global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename std::conditional<GEN == 1, FrontGenP, FrontFwdP>::type p) {
   constexpr int NUT = S / 8;                 // unit tiles = workgroups per row tile
   constexpr int QH = S / 64, QX = FS / 64;   // 8-k groups of the h / x panel per wave
   constexpr int NB = 2 * (FS / 16);          // projection tiles per row tile (2 x 16-clip subtiles)
@@ -708,6 +735,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
   static_assert(S % 128 == 0 && FS % 64 == 0 && NB <= NUT, "unsupported front shape");
   __shared__ float red[8 * 1024];
   __shared__ int s_dead;
+  __shared__ int s_exit;       // (generation mode) the loop ends here
   const int T = p.T, B = p.B;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5, li = lane & 15, g = lane >> 4;
@@ -781,6 +809,18 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
       for (int e = 0; e < 4; ++e) wpr[u][e] = v[e];
     }
   }
+  // generation mode: the stop head's weight in LDS, on the stop workgroups only.  (Not in registers: the fp32 form at S = 1024
+  // holds 243 VGPRs already and would spill; a lane reads its 4 / 8 contiguous k per 16-k unit with one / two ds_read_b128.)
+  const bool swg = GEN == 1 && ut < 2;
+  __shared__ __attribute__((aligned(16))) float wsl[GEN == 1 ? S : 4];
+  float bsv = 0.f;
+  if constexpr (GEN == 1) {
+    if (swg) {
+      for (int k = tid; k < S; k += 512) wsl[k] = p.ws[k];
+      bsv = p.bs[0];
+    }
+    __syncthreads();
+  }
 
   unsigned* flag_h = p.ctl.hdr + PS_FLAG_OFF + rt * NUT;
   unsigned* flag_x = p.ctl.hdr + PS_FLAG_OFF + p.nrt * NUT + rt * NB;
@@ -817,6 +857,18 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
     }
   };
   load_pre(0);
+  // generation mode: thread tid < 16 of a stop workgroup owns clip sm of its subtile (first stop, next uniform)
+  const int nsub = 2 * p.nrt, sub = 2 * rt + (ut & 1);
+  unsigned* gen_done = p.ctl.hdr + PS_GEN_OFF;
+  unsigned* gen_all = gen_done + 8;
+  const int sm = row0 + 16 * (ut & 1) + tid;
+  const bool sthr = swg && tid < 16 && sm < B;
+  int fst = T, t_ran = T;
+  bool all_pub = false;
+  float ureg = 1.f;
+  if constexpr (GEN == 1) {
+    if (sthr) ureg = p.u[sm];
+  }
   for (int t = 0; t < T; ++t) {
     f32x16 acc;
 #pragma unroll
@@ -824,11 +876,30 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
     if (t > 0) {
       const int par = (t - 1) & 1;
       // ---- h part (its flags were already waited for by the projection phase of frame t-1 on projection workgroups)
-      if (wid == 0 && alive) {
+      bool ex = false;
+      if constexpr (GEN == 1) {
+        // exit test on the final decisions of frame t - 1 - GEN_LAG (folded into the barrier of the h wait below)
+        if (wid == 0) {
+          if (t > GEN_LAG && alive) {
+            const unsigned want = (unsigned)(t - GEN_LAG);
+            alive = ps_wait_flags(p.ctl, gen_done, nsub, want, lane);
+            if (!alive) s_dead = 1;
+            else {
+              const unsigned a = lane < nsub ? __hip_atomic_load(gen_all + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
+              ex = __all(a != 0u && a <= want);
+            }
+          }
+          if (lane == 0) s_exit = ex ? 1 : 0;
+        }
+      }
+      if (wid == 0 && alive && !ex) {
         alive = ps_wait_flags(p.ctl, flag_h, NUT, (unsigned)t, lane);
         if (!alive) s_dead = 1;
       }
       __syncthreads();
+      if constexpr (GEN == 1) {
+        if (s_exit) { t_ran = t; break; }
+      }
       if (PM == 2) {
         const unsigned ab = (unsigned)(((int64_t)(par * p.nrt + rt) * hgs + (int64_t)l31 * 8) * 4);
         u32x4 a0[QH2], a1[QH2];
@@ -929,7 +1000,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
       __hip_atomic_store(flag_h + ut, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // this frame's pre-activations were consumed above (ig .. og hold what goes back into their place)
     if (t + 1 < T) load_pre(t + 1);
-    if (epi) {
+    if (GEN == 0 && epi) {      // (the generation mode keeps no history)
       if (CELL == 1) {
         float* pr = p.gates + ((int64_t)t * B + em) * 3 * S + eu;
         pr[0] = ig; pr[S] = fg; pr[2 * S] = gg;
@@ -950,6 +1021,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
       }
       __syncthreads();
       f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
+      float sdot = 0.f;          // (generation mode, stop workgroups) this lane's part of h_t . w_s
       if (PM == 2) {
         // lane (clip li, k slot g) takes k = 32U + 8g .. +7 = the whole row of unit tile 4U + g
         const unsigned ab = (unsigned)(((int64_t)((t & 1) * p.nrt + rt) * hgs + (int64_t)(16 * bsub + li) * 8) * 4);
@@ -963,6 +1035,20 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
 #pragma unroll
         for (int U = 0; U < UP2; ++U)
           pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ps_bf16x8b, ps_pack8(a0[U], a1[U])), wpb[U], pacc, 0, 0, 0);
+        if constexpr (GEN == 1) {
+          if (swg) {     // (the stop logit from the unrounded h_t)
+#pragma unroll
+            for (int U = 0; U < UP2; ++U) {
+              const float* wk = wsl + 32 * (wid * UP2 + U) + 8 * g;
+              const f32x4 w0 = *reinterpret_cast<const f32x4*>(wk), w1 = *reinterpret_cast<const f32x4*>(wk + 4);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                sdot = fmaf(__uint_as_float(a0[U][j]), w0[j], sdot);
+                sdot = fmaf(__uint_as_float(a1[U][j]), w1[j], sdot);
+              }
+            }
+          }
+        }
       } else {
         // A = h_t rows of the 16-clip subtile: lane (clip li, k slot g) takes k = 16u + 4g .. +3 = unit tile 2u + (g>>1), half g&1
         const unsigned ab = (unsigned)(((int64_t)((t & 1) * p.nrt + rt) * hgs + (int64_t)(16 * bsub + li) * 8 + 4 * (g & 1)) * 4);
@@ -970,6 +1056,16 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
 #pragma unroll
         for (int u = 0; u < UP; ++u)
           a[u] = __builtin_amdgcn_raw_buffer_load_b128(hr, ab + (unsigned)((2 * (wid * UP + u) + (g >> 1)) * 32 * 32), 0, 16);
+        if constexpr (GEN == 1) {
+          if (swg) {     // (the stop logit from the unrounded h_t)
+#pragma unroll
+            for (int u = 0; u < UP; ++u) {
+              const f32x4 w = *reinterpret_cast<const f32x4*>(wsl + 16 * (wid * UP + u) + 4 * g);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) sdot = fmaf(__uint_as_float(a[u][e]), w[e], sdot);
+            }
+          }
+        }
         if (p.rb) {
 #pragma unroll
           for (int u = 0; u < UP; ++u)
@@ -984,6 +1080,13 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
       // 16x16 tile: col = lane & 15, row = 4 * (lane >> 4) + e   (red is free again: the gate sums were consumed above)
 #pragma unroll
       for (int e = 0; e < 4; ++e) red[wid * 256 + (4 * g + e) * 16 + li] = pacc[e];
+      if constexpr (GEN == 1) {
+        if (swg) {       // the 4 k slots of a clip, then (below) the 8 waves: the same LDS pass as pacc
+          sdot += __shfl_xor(sdot, 16);
+          sdot += __shfl_xor(sdot, 32);
+          if (g == 0) red[2048 + wid * 16 + li] = sdot;
+        }
+      }
       __syncthreads();
       if (tid < 256) {
         float v = bbias;
@@ -996,12 +1099,40 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const FrontFwdP
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (bm < B) {
           p.x[(int64_t)bm * p.ldx + (int64_t)t * FS + col] = v;
-          if (p.xt) p.xt[((int64_t)t * B + bm) * FS + col] = v;
+          if (GEN == 0 && p.xt) p.xt[((int64_t)t * B + bm) * FS + col] = v;
+        }
+        if constexpr (GEN == 1) {
+          if (swg && wid == 0) {
+            // stop logit and draw of clip sm; then the subtile's words, published before the x flag below
+            if (sthr) {
+              float sv = bsv;
+#pragma unroll
+              for (int w = 0; w < 8; ++w) sv += red[2048 + w * 16 + tid];
+              if (s_dead) sv = __builtin_nanf("");
+              p.s[(int64_t)sm * p.lds + t] = sv;
+              if (fst == T && ureg < ag_sigmoid(sv)) fst = t + 1;
+            }
+            const bool all = __all(!sthr || fst <= t + 1);      // (clips past the batch count as stopped)
+            if (tid == 0) {
+              if (all && !all_pub) {
+                __hip_atomic_store(gen_all + sub, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                all_pub = true;
+              }
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // gen_all lands before gen_done says "frame t is final"
+              __hip_atomic_store(gen_done + sub, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            if (sthr && t + 1 < T) ureg = p.u[(int64_t)(t + 1) * B + sm];
+          }
         }
       }
       __syncthreads();
       if (tid == 0) __hip_atomic_store(flag_x + ut, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+  }
+  if constexpr (GEN == 1) {
+    if (sthr) p.first[sm] = fst;
+    if (blockIdx.x == 0 && tid == 0) *p.t_run = t_ran;
   }
 }
 
@@ -1097,6 +1228,61 @@ extern "C" int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x
   if (S == 1024) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 1>), dim3(grid), dim3(512), 0, st, p);
   else hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 1>), dim3(grid), dim3(512), 0, st, p);
   AG_CHECK_LAUNCH("ag_grufront_fwd_persist");
+  return AG_OK;
+}
+
+// Generation mode of the two fronts above (gfront_persist_fwd_kernel<..., GEN = 1>): the frame loop of a sample, no history.
+//   cell 0 (LSTM): pre [T,B,4S] = the z/c part of the pre-activations + both biases (as ag_gfront_fwd_persist's gates on input)
+//   cell 1 (GRU):  pre [T,B,3S] as ag_grufront_fwd_persist's gates on input; b_hn [S] = b_hh[2S:] (ignored for cell 0)
+//   w_s [S], b_s [1]: the stop head; u [T,B]: uniforms, stop[b,t] = u[t,b] < sigmoid(s[b,t])
+// Outputs: x [B,T*fs] (row pitch ldx) and s [B,T] (row pitch lds) for the frames run; first [B] (int32) = frames clip b
+// generates (1 + its first stop frame, T if it never stops); t_run [1] (int32) = frames run: the launch leaves its loop
+// GEN_LAG frames after every clip has stopped (max(first) + GEN_LAG when that is < T).  `pre` is only read.  Shapes and
+// workspace as ag_gfront_fwd_persist.
+extern "C" int ag_gfront_gen_persist(int cell, const float* pre, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
+                                     const float* w_p, const float* b_p, const float* w_s, const float* b_s, const float* u,
+                                     float* x, int64_t ldx, float* s, int64_t lds, int* first, int* t_run, void* ws,
+                                     int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream) {
+  AG_REQUIRE(cell == 0 || cell == 1, "ag_gfront_gen_persist: cell must be 0 (LSTM) or 1 (GRU)");
+  AG_REQUIRE(pre && w_x && w_hh && w_p && b_p && w_s && b_s && u && x && s && first && t_run && ws && (cell == 0 || b_hn),
+             "ag_gfront_gen_persist: null tensor");
+  AG_REQUIRE(T > 0, "ag_gfront_gen_persist: T must be positive");
+  AG_REQUIRE(ldx >= (int64_t)T * fs, "ag_gfront_gen_persist: x row pitch smaller than a row");
+  AG_REQUIRE(lds >= T, "ag_gfront_gen_persist: s row pitch smaller than a row");
+  if (!front_shape_ok(B, S, fs, n_cu)) {
+    ag_set_error("ag_gfront_gen_persist: shape B=%d S=%d fs=%d is not supported on %d CUs", B, S, fs, n_cu);
+    return AG_ERR_UNSUPPORTED;
+  }
+  AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
+             "ag_gfront_gen_persist: workspace too small or misaligned");
+  AG_REQUIRE(ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
+             "ag_gfront_gen_persist: weights must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
+    ag_set_error("ag_gfront_gen_persist: memset failed");
+    return AG_ERR_LAUNCH;
+  }
+  FrontGenP p;
+  p.gates = const_cast<float*>(pre);      // (read only in this mode)
+  p.gh = nullptr; p.bhn = cell == 1 ? b_hn : nullptr; p.wx = w_x; p.whh = w_hh; p.wp = w_p; p.bp = b_p;
+  p.hs = nullptr; p.cs = nullptr; p.x = x; p.ldx = ldx; p.xt = nullptr;
+  p.ws = w_s; p.bs = b_s; p.u = u; p.s = s; p.lds = lds; p.first = first; p.t_run = t_run;
+  p.ctl = ps_ctl(ws);
+  p.nrt = ag_cdiv(B, 32);
+  p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
+  p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
+  p.T = T; p.B = B; p.ldwx = ldwx; p.rb = ag_precision() == AG_PREC_BF16;
+  const int grid = p.nrt * (S / 8);
+  // (the same kernels as the training forward: the GRU front and S = 128 have no bf16-MFMA form)
+  if (S == 1024) {
+    if (cell == 1) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 1, 1>), dim3(grid), dim3(512), 0, st, p);
+    else if (p.rb) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 2, 0, 1>), dim3(grid), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 0, 1>), dim3(grid), dim3(512), 0, st, p);
+  } else {
+    if (cell == 1) hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 1, 1>), dim3(grid), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 0, 1>), dim3(grid), dim3(512), 0, st, p);
+  }
+  AG_CHECK_LAUNCH("ag_gfront_gen_persist");
   return AG_OK;
 }
 

@@ -1330,6 +1330,36 @@ def grufront_fwd_persist(gates, gh, wx, whh, bhn, wp, bp, hs, x, xt=None):
           'ag_grufront_fwd_persist')
 
 
+def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=None):
+    """the generation mode of the fronts' persistent launch (ag_gfront_gen_persist): the frame loop of a sample, no history.
+    pre [T,B,4S] (LSTM front) or [T,B,3S] (GRU front, then ``bhn`` [S] = b_hh[2S:]) is only read; ws = the stop head's
+    weight (S elements), bs [1]; u [T,B] uniforms.  Writes x [B, T*fs] (rows of any pitch: channel 0 of the conv trunk's
+    slab), s [B,T] (rows of any pitch >= T), first [B] int32 (frames per clip) and t_run [1] int32 (frames run), all for
+    the frames run only (see include/audiogan_hip.h)."""
+    T, B, SG = pre.shape
+    S = whh.size(1)
+    fs = wp.size(0)
+    cell = 1 if SG == 3 * S else 0
+    assert SG == (3 if cell else 4) * S, (tuple(pre.shape), tuple(whh.shape))
+    for t_, n, shp in ((pre, 'pre', (T, B, SG)), (whh, 'whh', (SG, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
+                       (bs, 'bs', (1,)), (u, 'u', (T, B))) + (((bhn, 'bhn', (S,)),) if cell else ()):
+        _chk(t_, n)
+        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
+    _chk(ws, 'ws')
+    assert ws.is_contiguous() and ws.numel() == S, tuple(ws.shape)
+    ldx, lds = _rows(x, 'x', B, T * fs), _rows(s, 's', B, T)
+    for t_, n, shp in ((first, 'first', (B,)), (t_run, 't_run', (1,))):
+        _chk(t_, n, torch.int32)
+        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
+    _chk(wx, 'wx')
+    assert tuple(wx.shape) == (SG, fs) and wx.stride(1) == 1
+    nb = int(lib.ag_gfront_persist_ws_bytes(B, S, fs))
+    wsp = _persist_workspace(x.device, nb)
+    check(lib.ag_gfront_gen_persist(cell, _p(pre), _p(wx), wx.stride(0), _p(whh), _p(bhn if cell else None), _p(wp), _p(bp),
+                                    _p(ws), _p(bs), _p(u), _p(x), ldx, _p(s), lds, _p(first), _p(t_run), _p(wsp), wsp.numel(),
+                                    T, B, S, fs, _n_cu(x.device), _stream()), 'ag_gfront_gen_persist')
+
+
 def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):
     T, B, S3 = gates.shape
     S, fs = S3 // 3, wp.size(0)

@@ -20,7 +20,13 @@ iteration, generator iteration - are captured ONCE into three hipGraphs over sta
 is uploaded into the static tensors and z / the instance noise are drawn in place on the device before each replay.  The
 iterations run with ``host=False, check=False`` (no host read inside a graph): accuracies and the REINFORCE baseline are
 device scalars; the accuracy test of :813 reads two of them back after the replay, as the reference does after its
-iteration.  ~3000 launches per pass are then paced by the GPU, not by the Python interpreter."""
+iteration.  ~3000 launches per pass are then paced by the GPU, not by the Python interpreter.
+
+Samples (:922-935): with ``sample_every`` > 0, every ``sample_every``-th generator iteration is followed by an eager
+``Generator.generate`` from fixed words and a fixed z, in eager and graphed loops alike; its stop draws come from a private
+``torch.Generator``, so sampling changes no training bit.  ``sample_dir``: every ``audio_every``-th generator iteration the
+samples are also written as WAV files (audio.write_wav), each cut to its clip's length."""
+import os
 import time
 
 import numpy as np
@@ -33,12 +39,21 @@ class TrainLoop(object):
     def __init__(self, g, d, e_g, e_d, opt_g, opt_d, loader, pick_words, batch_size, maxlen, device, noisescale=0.01,
                  critic_iter=100, require_acc=0.5, gencatchup=1, dgradclip=1.0, ggradclip=0.1, g_optim='boundary_seeking',
                  checkpoint_every=500, checkpoint_prefix=None, fixed_critic_iter=None, stop=None, check=True, graphed=False,
-                 host=None):
+                 host=None, sample_every=0, sample_words=None, sample_z=None, sample_seed=0, on_sample=None, sample_dir=None,
+                 audio_every=500):
         """``loader``: the generator ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths, keys, cseq,
         clen], dataset.py:91); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
         (``dataset.pick_words(..., skip_samples=True)[1:3]``, audiogan.py:715-716); ``stop``: None = Bernoulli stop draws
         like the reference (a host sync per generator forward), 'never' = fixed-length clips.  ``opt_d`` holds the parameters
-        of d and e_d, ``opt_g`` those of g and e_g (:690-691)."""
+        of d and e_d, ``opt_g`` those of g and e_g (:690-691).
+
+        Sampling (off by default; the reference samples every 20 generator iterations and writes audio every 500):
+        ``sample_every``: sample after every such generator iteration (0 = never); ``sample_words``: (cseq, clen) of the
+        ``batch_size`` fixed words (:672-681; required - drawing them from ``pick_words`` would move the loader's stream);
+        ``sample_z``: the fixed [batch_size, T, noise] z (default: drawn once from ``sample_seed``); ``on_sample(gen_iter, wave,
+        length, stop_list)``: receives every sample; ``sample_dir`` / ``audio_every``: write the samples of every
+        ``audio_every``-th generator iteration to ``<sample_dir>/sample-<gen_iter>-<i>.wav``.  The uniforms of the last sample's
+        stop draws are kept in ``last_sample_u``."""
         self.g, self.d, self.e_g, self.e_d, self.opt_g, self.opt_d = g, d, e_g, e_d, opt_g, opt_d
         self.loader, self.pick_words = loader, pick_words
         self.B, self.maxlen, self.dev = batch_size, maxlen, torch.device(device)
@@ -63,6 +78,16 @@ class TrainLoop(object):
         self.gpu_timeline = None         # set to a list to record (key, start event, end event, host time) per replay
         if self.graphed:
             assert stop == 'never' and self.dev.type == 'cuda', "graphed=True needs stop='never' and a CUDA device"
+        self.sample_every, self.sample_dir, self.audio_every = int(sample_every or 0), sample_dir, int(audio_every or 0)
+        self.on_sample, self._sample_words, self.last_sample_u = on_sample, sample_words, None
+        self._sample_rng = self.sample_z = None
+        if self.sample_every or self.sample_dir is not None:
+            assert sample_words is not None, 'sampling needs sample_words=(cseq, clen)'
+            # a private generator: the sample's draws leave the training streams alone
+            self._sample_rng = torch.Generator(device=self.dev).manual_seed(int(sample_seed))
+            if sample_z is None:
+                sample_z = torch.randn(batch_size, self.nframes, g._noise_size, device=self.dev, generator=self._sample_rng)
+            self.sample_z = sample_z.to(self.dev)
 
     # ---- minibatch pieces ---------------------------------------------------------------
     def _up(self, a, dtype):
@@ -204,6 +229,30 @@ class TrainLoop(object):
         h['replay'] += (t1 - t0) * 1e3; h['loader'] += (t2 - t1) * 1e3; h['stage'] += (t3 - t2) * 1e3
         h['loader_max'] = max(h.get('loader_max', 0.0), (t2 - t1) * 1e3); h['replay_max'] = max(h.get('replay_max', 0.0), (t1 - t0) * 1e3)
 
+    # ---- samples (audiogan.py:922-935) ------------------------------------------------------------
+    def _maybe_sample(self):
+        n = self.gen_iter
+        want = self.sample_every > 0 and n % self.sample_every == 0
+        audio = self.sample_dir is not None and self.audio_every > 0 and n % self.audio_every == 0
+        if not (want or audio):
+            return None
+        cs, cl = self._sample_words
+        cs = cs.to(self.dev).long() if torch.is_tensor(cs) else self._up(cs, torch.long)
+        cl = cl.to(self.dev).long() if torch.is_tensor(cl) else self._up(cl, torch.long)
+        with torch.no_grad():
+            u = torch.rand(self.nframes, self.B, device=self.dev, generator=self._sample_rng)
+            self.last_sample_u = u
+            wave, _, stop_list, length = self.g.generate(self.e_g(cs, cl), z=self.sample_z, u=u)
+        if want and self.on_sample is not None:
+            self.on_sample(n, wave, length, stop_list)
+        if audio:
+            from .audio import write_wav
+            os.makedirs(self.sample_dir, exist_ok=True)
+            w, ln = wave.cpu().numpy(), length.cpu().numpy()
+            for i in range(w.shape[0]):
+                write_wav(os.path.join(self.sample_dir, 'sample-%05d-%d.wav' % (n, i)), w[i, :int(ln[i])])
+        return wave, length, stop_list
+
     # ---- iterations -----------------------------------------------------------------------
     def d_iteration(self):
         if self.graphed:
@@ -240,6 +289,7 @@ class TrainLoop(object):
             self._replay('g')
             self.baseline = self._static['baseline']
             self._maybe_checkpoint()
+            self._maybe_sample()
             return self._out['g']
         self.gen_iter += 1
         real, real_len, _, _ = self._real()
@@ -250,6 +300,7 @@ class TrainLoop(object):
                               self.baseline, self.ggradclip, self.g_optim, check=self.check, host=self.host)
         self.baseline = r['baseline']
         self._maybe_checkpoint()
+        self._maybe_sample()
         return r
 
     def outer(self):

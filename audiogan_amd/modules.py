@@ -235,6 +235,58 @@ class Generator(nn.Module):
         wave = ops.GTrunkFn.apply(x, self._trunk, *self._trunk.group.params())
         return wave, s, stop_list, out_len
 
+    def refresh_weights(self):
+        """materialise the weight-normed weights of both blocks NOW, whatever the cache says.  A captured optimiser step rewrites
+        the parameters through raw pointers and bumps neither their versions nor their epochs, so after graph replays an eager
+        forward could find its old cache key "current" and run on stale weights; ``generate`` calls this first.  (The training
+        path keeps its cache rule: re-materialising unchanged parameters writes the same bits.)"""
+        for gr in (self._front.group, self._trunk.group):
+            gr._key = None
+        self.prepare_weights()
+
+    @torch.no_grad()
+    def generate(self, c, length=None, z=None, u=None, generator=None):
+        """Sample clips (audiogan.py:444-468 without training): returns (wave, s, stop_list, length) like ``forward``, every
+        tensor detached, no autograd graph.  ``c`` [B, embed]; ``z`` [B,T,noise] or None (drawn like ``forward`` does, for
+        ``length`` samples, from ``generator``); ``u`` [T,B] uniforms or None (``torch.rand(T, B, generator=generator)`` on
+        the device).  Clip b stops at the first frame t with u[t,b] < sigmoid(s[b,t]) (the reference's Bernoulli draw) and
+        keeps the frames up to and including it: length[b] = first[b] * frame_size.  The frame loop ends once every clip
+        has stopped and reads the host ONCE (t_eff = max(first); the reference reads it once per frame); the conv trunk
+        runs on the first t_eff frames.  ``self.last_t_run``: the frames the persistent loop ran (device int32 [1]), or None
+        when the per-frame fallback ran all T."""
+        from .recurrent import front_sample
+        fs, ns, es = self._frame_size, self._noise_size, self._embed_size
+        dev = c.device
+        batch_size = c.size(0)
+        if z is None:
+            nframes = div_roundup(length, fs)
+            z = torch.randn(batch_size, nframes, ns, device=dev, generator=generator)
+        else:
+            z = z.to(dev)
+            batch_size, nframes, _ = z.size()
+        self.refresh_weights()
+        if z.is_cuda and z.dtype == torch.float32 and c.dtype == torch.float32:
+            zc = ops.BuildZCFn.apply(z, c)
+        else:
+            zc = torch.cat([z, c.unsqueeze(1).expand(batch_size, nframes, es)], 2).transpose(0, 1).contiguous()
+        if u is None:
+            u = torch.rand(nframes, batch_size, device=dev, generator=generator)
+        u = u.to(dev, torch.float32)
+        assert tuple(u.shape) == (nframes, batch_size), (tuple(u.shape), (nframes, batch_size))
+        x, s, first, self.last_t_run = front_sample(self._front, zc, u)
+        t_eff = int(first.max())          # the one host read
+        x, s = x[:, :t_eff * fs], s[:, :t_eff]
+        # the draws of the frames kept: u < sigmoid(s), with each clip's first stop where ``first`` puts it (the launch drew
+        # it with its own sigmoid; the two can only disagree within an ulp of the threshold).  first = T is also "never".
+        tt = torch.arange(t_eff, device=dev).view(1, -1)
+        fm1 = (first - 1).view(-1, 1)
+        draws = (u[:t_eff].t() < torch.sigmoid(s)).long()
+        stops = torch.where(tt < fm1, torch.zeros_like(draws),
+                            torch.where((tt == fm1) & (fm1 < nframes - 1), torch.ones_like(draws), draws))
+        stop_list = [stops[:, t:t + 1] for t in range(t_eff)]
+        wave = ops.GTrunkFn.apply(x, self._trunk, *self._trunk.group.params())
+        return wave, s, stop_list, first * fs
+
 
 _NEVER = {}
 

@@ -1,7 +1,8 @@
 """Recurrent blocks of the hot path.
 
-  LSTMSeqFn  NN.LSTM layer over a padded batch      audiogan.py:498-503, :543, :214-229, :315
-  GFrontFn   LSTMCell stack + tanh(proj) feedback   audiogan.py:377-386, :409-410, :428-460
+  LSTMSeqFn     NN.LSTM layer over a padded batch      audiogan.py:498-503, :543, :214-229, :315
+  GFrontFn      LSTMCell stack + tanh(proj) feedback   audiogan.py:377-386, :409-410, :428-460
+  front_sample  the same frame loop for sampling       audiogan.py:444-460 (stop draws, early exit), :922-935
 
 The per-time-step work is a product with only B (clips per GPU) rows.  When shapes allow
 (B <= 64, sizes multiples of 8, 16-byte aligned rows -- true for every BASELINE config) the
@@ -692,3 +693,52 @@ class GRUFrontFn(torch.autograd.Function):
             K.gemm(dgi2, w_ih[:, fs:], dzc)
             dzc = dzc.view(T, B, Fz)
         return (dzc, None) + tuple(front.group.backward(dws) if wg else [None] * (2 * len(front.group.items)))
+
+
+# --------------------------------------------------------------------------------------
+# Sampling (Generator.generate): the frame loop with the stop draws, no autograd, no history
+# --------------------------------------------------------------------------------------
+def first_stops(stops, T):
+    """[B,T'] 0/1 draws -> int64 [B]: the frames each clip generates, up to and including its first stop draw (T if none:
+    audiogan.py:451-458)"""
+    return torch.where(stops.bool().any(1), stops.long().argmax(1) + 1, torch.full_like(stops[:, 0].long(), T))
+
+
+def front_sample(front, zc, u):
+    """the frame loop of a sample (``GFront`` or ``GRUFront``): zc [T,B,Fz] contiguous, u [T,B] uniforms; clip b stops at frame
+    t when u[t,b] < sigmoid(s[b,t]) (the reference's Bernoulli draw, :450).  Returns (x [B, T*fs], s [B,T], first int64 [B])
+    where first[b] = the frames clip b generates; only the first max(first) frames of x and s are meaningful.
+
+    Where the persistent launch fits (one layer, a supported (B, S, fs)): ONE ag_gfront_gen_persist launch, which draws the
+    stops itself, keeps no history and leaves its frame loop one frame after every clip has stopped.  Otherwise the training
+    front runs over all T frames under no_grad and the same rule is applied to its logits."""
+    T, B, Fz = zc.shape
+    fs, S = front.fs, front.ss
+    gru = isinstance(front, GRUFront)
+    nl = 1 if gru else front.nl
+    dev = zc.device
+    prep = front.group.prepare()
+    w_ih, w_hh, b_ih, b_hh = [p_.w for p_ in prep[:4]]
+    pw, pb, sw, sb = [p_.w for p_ in prep[4 * nl:4 * nl + 4]]
+    wx, wz = w_ih[:, :fs], w_ih[:, fs:]
+    if nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev):
+        zc2 = zc.contiguous().view(T * B, Fz)
+        if gru:
+            pre = torch.empty(T, B, 3 * S, device=dev)
+            bias = b_ih.clone()
+            bias[:2 * S] += b_hh[:2 * S]
+            K.gemm(zc2, wz, pre.view(T * B, 3 * S), tb=True, bias=bias)
+        else:
+            pre = torch.empty(T, B, 4 * S, device=dev)
+            K.gemm(zc2, wz, pre.view(T * B, 4 * S), tb=True, bias=b_ih, res=_bcast_rows(b_hh, T * B))
+        x = _frames_buffer(front, B, T * fs, dev)
+        s = torch.empty(B, T, device=dev)
+        first = torch.empty(B, dtype=torch.int32, device=dev)
+        t_run = torch.empty(1, dtype=torch.int32, device=dev)
+        K.gfront_gen_persist(pre, wx, w_hh, pw, pb, sw.view(-1), sb, u.contiguous(), x, s, first, t_run,
+                             bhn=b_hh[2 * S:].contiguous() if gru else None)
+        return x, s, first.long(), t_run
+    with torch.no_grad():
+        fn = GRUFrontFn if gru else GFrontFn
+        x, s = fn.apply(zc, front, *front.group.params())
+    return x, s, first_stops(u.t() < torch.sigmoid(s), T), None

@@ -438,6 +438,22 @@ int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x, int ldwx,
                             const float* w_p, const float* b_p, float* hs, float* x, int64_t ldx, float* xt, void* ws,
                             int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream);
 
+/* (v11) Generation mode of the two fronts above: the frame loop of a SAMPLE (Generator.generate), trains nothing and keeps no
+ * history - gates, hidden / cell states and time-major frames are not written.  cell 0 (LSTM): pre [T,B,4S] as
+ * ag_gfront_fwd_persist's gates on input; cell 1 (GRU): pre [T,B,3S] as ag_grufront_fwd_persist's gates on input, b_hn [S]
+ * (ignored, may be NULL, for cell 0); pre is only read.  Per frame the launch also forms the stop logit s[b,t] = h_t[b] . w_s +
+ * b_s (w_s [S], b_s [1]: the materialised stop head) and draws stop[b,t] = u[t,b] < sigmoid(s[b,t]) from the caller's
+ * uniforms u [T,B] (audiogan.py:444-460: a Bernoulli(p) draw, stated as a function of u so that it can be reproduced).
+ * Outputs: the frames x [B,T*fs] (row pitch ldx) and s [B,T] (row pitch lds >= T) of the frames run; first [B] (int32) = the
+ * frames clip b generates (1 + its first stop frame, T if it never stops); t_run [1] (int32) = the frames run.  The loop ends
+ * early, by one rule every workgroup takes from the same write-once words: before frame t + 1 it reads the decisions of
+ * frame t - 1 (a lag of one frame) and leaves iff every clip has stopped by then, so t_run = min(T, max(first) + 1).  Frames
+ * past max(first) are correct frames the caller discards.  Shapes and workspace as for ag_gfront_fwd_persist. */
+int ag_gfront_gen_persist(int cell, const float* pre, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
+                          const float* w_p, const float* b_p, const float* w_s, const float* b_s, const float* u, float* x,
+                          int64_t ldx, float* s, int64_t lds, int* first, int* t_run, void* ws, int64_t ws_bytes, int T, int B,
+                          int S, int fs, int n_cu, void* stream);
+
 /* One fused backward step of the Generator front (audiogan.py:428-460: LSTMCell -> tanh(Linear) fed back), frame t:
  *   gx     = dxa * (1 - x_t^2)                        d(pre-tanh) of the projection, stored to gx_out [B,Kp]
  *   dh     = dh_acc + gx * w_proj                      w_proj [Kp = frame size, H]; dh_acc [B,H] rows, pitch lddh
