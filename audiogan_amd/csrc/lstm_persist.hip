@@ -91,14 +91,22 @@ struct PersistFwdP {
   int rb;              // AG_PREC_BF16: both operands of the recurrent product rounded to bf16
 };
 
+// LE64: the caller guarantees n <= 64 where n is only known at run time - one predicated load per poll instead of a loop
+// with a run-time trip count (which cost the fronts' forward 1.5 us per frame when the number of projection tiles became a
+// run-time value)
+template <bool LE64 = false>
 __device__ __forceinline__ bool ps_wait_flags(const PersistCtl& ctl, const unsigned* flags, int n, unsigned want, int lane) {
   unsigned* hdr = ctl.hdr;
   // ONE wave polls the group's flags (lane i <-> flags i, i + 64, ...), relaxed agent-scope loads
   unsigned long long t0 = 0;
   for (unsigned spins = 0;; ++spins) {
     bool ok = true;
-    for (int i = lane; i < n; i += 64)
-      ok &= __hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
+    if (LE64) {
+      if (lane < n) ok = __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
+    } else {
+      for (int i = lane; i < n; i += 64)
+        ok &= __hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
+    }
     if (__all(ok)) return true;
     if ((spins & 63) == 63) {
       if (__hip_atomic_load(hdr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;   // somebody gave up
@@ -670,11 +678,18 @@ extern "C" int ag_lstm_seq_bwd_persist(const float* const* gates, const float* c
 //   [W_hh] panel and fs/8 rows of the [W_x] panel as MFMA B operands (80 VGPRs at S = 1024, fs = 256).
 //   phase A, frame t: h_{t-1} part of the product as soon as the group's h flags are up, x_{t-1} part when the
 //   projection tiles are up, LDS sum over the waves, cell, h_t published (write-through) + flag.
-//   phase B, frame t (workgroups ut < 2*fs/16 only): one [16 clips x 16 frame samples] tile of x_t = tanh(h_t W_p^T + b):
+//   phase B, frame t (workgroups ut < 2*ceil(fs/16) only): one [16 clips x 16 frame samples] tile of x_t = tanh(h_t W_p^T + b):
 //   waits for all h_t of its clips, v_mfma_f32_16x16x4_f32 against its resident W_p panel, publishes x_t + flag.
 //   The h part of frame t+1 (80 % of the MFMAs) overlaps phase B of frame t on the other workgroups.
 // Exchange buffers ([parity][rt][8-unit tile][32 clips][8], as in the layer kernels) hold h and x; two parities are
 // enough (h_{t+1} / x_{t+1} are written only after every reader of h_{t-1} / x_{t-1} has finished frame t).
+//
+// Frame sizes below the panel width: the template parameter FS is the PADDED width of the x panel (256 at S = 1024, 64 at
+// S = 128), the real frame size p.fs (a multiple of 8, <= FS) is a run-time field.  k lanes of the W_x panel at or past fs
+// hold zeros (masked, not loaded: to the right of column fs in a row of W_ih lie the z/c weights), the 2 * ceil(fs / 16)
+// projection workgroups take rows of W_p / b_p past fs as zeros, the 8-column groups of the x exchange buffer past fs are
+// zeroed once by the projection workgroups before their first flag, and every global row uses fs as its pitch.  At
+// fs == FS nothing is masked and the arithmetic and its order are those of the fixed-width form.
 // ------------------------------------------------------------------------------------------
 struct FrontFwdP {
   float* gates;        // [T,B,4S] in: pre; out: activated gates
@@ -690,9 +705,10 @@ struct FrontFwdP {
   float* gh;           // GRU cell only: [T,B,3S], the n slot receives W_hn h + b_hn (what the backward needs)
   const float* bhn;    // GRU cell only: b_hh[2S:3S]
   float* hx;           // exchange: h   [2][nrt][S/8][32][8]
-  float* xx;           // exchange: x   [2][nrt][fs/8][32][8]
+  float* xx;           // exchange: x   [2][nrt][FS/8][32][8]  (FS = the padded panel width)
   PersistCtl ctl;
   int T, B, ldwx, nrt, rb;
+  int fs;              // the real frame size: fs % 8 == 0, 8 <= fs <= FS
 };
 
 // Generation mode (GEN = 1, ag_gfront_gen_persist): sampling, no autograd.  No history is written (gates, hs, cs, gh, xt:
@@ -730,13 +746,14 @@ template <int S, int FS, int PM, int CELL = 0, int GEN = 0>
 __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename std::conditional<GEN == 1, FrontGenP, FrontFwdP>::type p) {
   constexpr int NUT = S / 8;                 // unit tiles = workgroups per row tile
   constexpr int QH = S / 64, QX = FS / 64;   // 8-k groups of the h / x panel per wave
-  constexpr int NB = 2 * (FS / 16);          // projection tiles per row tile (2 x 16-clip subtiles)
+  constexpr int NBMAX = 2 * (FS / 16);       // projection tiles per row tile at fs == FS (2 x 16-clip subtiles)
   constexpr int UP = S / 128;                // 16-k units of W_p per wave
-  static_assert(S % 128 == 0 && FS % 64 == 0 && NB <= NUT, "unsupported front shape");
+  static_assert(S % 128 == 0 && FS % 64 == 0 && NBMAX <= NUT && NBMAX <= 64, "unsupported front shape");
   __shared__ float red[8 * 1024];
   __shared__ int s_dead;
   __shared__ int s_exit;       // (generation mode) the loop ends here
-  const int T = p.T, B = p.B;
+  const int T = p.T, B = p.B, fs = p.fs;
+  const int NB = 2 * ((fs + 15) >> 4);       // projection tiles per row tile (the last column tile is half valid at fs % 16 == 8)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5, li = lane & 15, g = lane >> 4;
   if (tid == 0) s_dead = 0;
@@ -759,9 +776,13 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
     }
 #pragma unroll
     for (int Q = 0; Q < QX2; ++Q) {
-      const float* src = p.wx + (int64_t)wrow * p.ldwx + (wid * QX + 2 * Q + hh) * 8;
-      const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
-      ps_u32x4 r = {ag_pack_bf16(a[0], a[1]), ag_pack_bf16(a[2], a[3]), ag_pack_bf16(b[0], b[1]), ag_pack_bf16(b[2], b[3])};
+      const int kx = (wid * QX + 2 * Q + hh) * 8;
+      ps_u32x4 r = {0u, 0u, 0u, 0u};
+      if (kx < fs) {          // (k >= fs: zeros - what lies there in the row are the z/c weights)
+        const float* src = p.wx + (int64_t)wrow * p.ldwx + kx;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
+        r = ps_u32x4{ag_pack_bf16(a[0], a[1]), ag_pack_bf16(a[2], a[3]), ag_pack_bf16(b[0], b[1]), ag_pack_bf16(b[2], b[3])};
+      }
       wxb[Q] = __builtin_bit_cast(ps_bf16x8, r);
     }
   } else {
@@ -778,14 +799,16 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
     }
 #pragma unroll
     for (int q = 0; q < QX; ++q) {
-      const f32x4 v = xz ? f32x4{0.f, 0.f, 0.f, 0.f}
-                         : ag_rbf4_if(*reinterpret_cast<const f32x4*>(p.wx + (int64_t)wrowx * p.ldwx + (wid * QX + q) * 8 + 4 * hh), p.rb);
+      const int kx = (wid * QX + q) * 8 + 4 * hh;       // (k >= fs: zeros - what lies there in the row are the z/c weights)
+      const f32x4 v = (xz || kx >= fs) ? f32x4{0.f, 0.f, 0.f, 0.f}
+                                       : ag_rbf4_if(*reinterpret_cast<const f32x4*>(p.wx + (int64_t)wrowx * p.ldwx + kx), p.rb);
 #pragma unroll
       for (int e = 0; e < 4; ++e) wxr[q][e] = v[e];
     }
   }
   const bool bwg = ut < NB;                  // this workgroup also owns a projection tile
   const int bsub = ut & 1, bcol0 = (ut >> 1) * 16;
+  const bool wpv = bwg && bcol0 + li < fs;   // this lane's row of W_p exists (rows past fs read as zeros)
   constexpr int UPf = PM == 2 ? 1 : UP, UP2 = PM == 2 ? UP / 2 : 1;
   float wpr[UPf][4];
   ps_bf16x8b wpb[UP2];
@@ -793,7 +816,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
 #pragma unroll
     for (int U = 0; U < UP2; ++U) {
       ps_u32x4 r = {0u, 0u, 0u, 0u};
-      if (bwg) {
+      if (wpv) {
         const float* src = p.wp + (int64_t)(bcol0 + li) * S + (wid * UP2 + U) * 32 + 8 * g;
         const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
         r = ps_u32x4{ag_pack_bf16(a[0], a[1]), ag_pack_bf16(a[2], a[3]), ag_pack_bf16(b[0], b[1]), ag_pack_bf16(b[2], b[3])};
@@ -803,7 +826,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
   } else {
 #pragma unroll
     for (int u = 0; u < UPf; ++u) {
-      const f32x4 v = bwg ? ag_rbf4_if(*reinterpret_cast<const f32x4*>(p.wp + (int64_t)(bcol0 + li) * S + (wid * UP + u) * 16 + 4 * g), p.rb)
+      const f32x4 v = wpv ? ag_rbf4_if(*reinterpret_cast<const f32x4*>(p.wp + (int64_t)(bcol0 + li) * S + (wid * UP + u) * 16 + 4 * g), p.rb)
                           : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int e = 0; e < 4; ++e) wpr[u][e] = v[e];
@@ -838,8 +861,19 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
   // phase B epilogue role: thread (clip row within the 16-row subtile, column), tid < 256
   const int brow = tid >> 4, bcl = tid & 15;
   const int bm = row0 + 16 * bsub + brow;
-  const float bbias = (bwg && tid < 256) ? p.bp[bcol0 + bcl] : 0.f;
+  const bool bcv = bcol0 + bcl < fs;         // this thread's frame sample exists
+  const float bbias = (bwg && tid < 256 && bcv) ? p.bp[bcol0 + bcl] : 0.f;
   bool alive = true;
+  // fs < FS: the 8-column groups of the x exchange buffer from roundup(fs, 16) / 8 on have no owner; the projection workgroups
+  // share them out and write zeros into both parities once.  Every wave drains its stores before the barrier in front of the
+  // workgroup's first x flag, and a reader of x waits for all NB flags, so the zeros are in place before the first read.
+  if (bwg && tid < 256) {
+    for (int gp = NB + ut; gp < FS / 8; gp += NB) {
+#pragma unroll
+      for (int par = 0; par < 2; ++par)
+        __builtin_amdgcn_raw_buffer_store_b32(0u, xr, (unsigned)(((int64_t)(par * p.nrt + rt) * xgs + (int64_t)gp * 256 + tid) * 4), 0, 16);
+    }
+  }
 
   // (the pre-activations of frame t + 1 are requested at the end of frame t, after the flag and before the trailing stores, and
   // nothing is written at the top of the loop - as in lstm_persist_fwd_kernel, where the re-initialisation of these registers made
@@ -929,7 +963,7 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
       }
       // ---- x part
       if (wid == 0 && alive) {
-        alive = ps_wait_flags(p.ctl, flag_x, NB, (unsigned)t, lane);
+        alive = ps_wait_flags<true>(p.ctl, flag_x, NB, (unsigned)t, lane);
         if (!alive) s_dead = 1;
       }
       __syncthreads();
@@ -1094,12 +1128,12 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
         for (int w = 0; w < 8; ++w) v += red[w * 256 + tid];
         v = s_dead ? __builtin_nanf("") : tanhf(v);
         const int col = bcol0 + bcl;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bm < B ? v : 0.f), xr,
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bm < B && bcv ? v : 0.f), xr,
             (unsigned)(((int64_t)((t & 1) * p.nrt + rt) * xgs + ((int64_t)(col >> 3) * 32 + 16 * bsub + brow) * 8 + (col & 7)) * 4), 0, 16);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (bm < B) {
-          p.x[(int64_t)bm * p.ldx + (int64_t)t * FS + col] = v;
-          if (GEN == 0 && p.xt) p.xt[((int64_t)t * B + bm) * FS + col] = v;
+        if (bm < B && bcv) {
+          p.x[(int64_t)bm * p.ldx + (int64_t)t * fs + col] = v;
+          if (GEN == 0 && p.xt) p.xt[((int64_t)t * B + bm) * fs + col] = v;
         }
         if constexpr (GEN == 1) {
           if (swg && wid == 0) {
@@ -1136,8 +1170,13 @@ __global__ __launch_bounds__(512) void gfront_persist_fwd_kernel(const typename 
   }
 }
 
+// the padded width of the x panel (the kernels' FS) for a state size, 0 = no instantiation; the fronts take every frame
+// size fs % 8 == 0 with 8 <= fs <= this width
+static int front_panel(int S) { return S == 1024 ? 256 : S == 128 ? 64 : 0; }
+static bool front_fs_ok(int S, int fs) { return fs >= 8 && fs % 8 == 0 && fs <= front_panel(S); }
+
 static bool front_shape_ok(int B, int S, int fs, int n_cu) {
-  if (!((S == 1024 && fs == 256) || (S == 128 && fs == 64))) return false;
+  if (!front_fs_ok(S, fs)) return false;
   if (B < 1 || B > 64) return false;
   if (n_cu > 256) n_cu = 256;
   return ag_cdiv(B, 32) * (S / 8) <= n_cu;
@@ -1146,7 +1185,9 @@ static bool front_shape_ok(int B, int S, int fs, int n_cu) {
 extern "C" int ag_gfront_persist_ok(int B, int S, int fs, int n_cu) { return front_shape_ok(B, S, fs, n_cu) ? 1 : 0; }
 
 extern "C" int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs) {
-  return PS_STICKY_BYTES + PS_HDR_BYTES + (int64_t)2 * ag_cdiv(B, 32) * 32 * (S + fs) * 4;
+  // (the x exchange buffer has the padded panel width whatever fs is; shapes outside the set: the formula of the exact width)
+  const int w = front_fs_ok(S, fs) ? front_panel(S) : fs;
+  return PS_STICKY_BYTES + PS_HDR_BYTES + (int64_t)2 * ag_cdiv(B, 32) * 32 * (S + w) * 4;
 }
 
 // One launch for the whole frame loop of the Generator front (one LSTMCell layer).  gates [T,B,4S]: in = the z/c
@@ -1164,7 +1205,7 @@ extern "C" int ag_gfront_fwd_persist(float* gates, const float* w_x, int ldwx, c
   }
   AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
              "ag_gfront_fwd_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
+  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
              "ag_gfront_fwd_persist: weights must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
@@ -1178,7 +1219,7 @@ extern "C" int ag_gfront_fwd_persist(float* gates, const float* w_x, int ldwx, c
   p.nrt = ag_cdiv(B, 32);
   p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
   p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.rb = ag_precision() == AG_PREC_BF16;
+  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
   const int grid = p.nrt * (S / 8);
   if (S == 1024) {
     if (p.rb) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 2>), dim3(grid), dim3(512), 0, st, p);
@@ -1209,7 +1250,7 @@ extern "C" int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x
   }
   AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
              "ag_grufront_fwd_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
+  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
              "ag_grufront_fwd_persist: weights must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
@@ -1223,7 +1264,7 @@ extern "C" int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x
   p.nrt = ag_cdiv(B, 32);
   p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
   p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.rb = ag_precision() == AG_PREC_BF16;
+  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
   const int grid = p.nrt * (S / 8);
   if (S == 1024) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 1>), dim3(grid), dim3(512), 0, st, p);
   else hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 1>), dim3(grid), dim3(512), 0, st, p);
@@ -1255,7 +1296,7 @@ extern "C" int ag_gfront_gen_persist(int cell, const float* pre, const float* w_
   }
   AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
              "ag_gfront_gen_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
+  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
              "ag_gfront_gen_persist: weights must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
@@ -1271,7 +1312,7 @@ extern "C" int ag_gfront_gen_persist(int cell, const float* pre, const float* w_
   p.nrt = ag_cdiv(B, 32);
   p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
   p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.rb = ag_precision() == AG_PREC_BF16;
+  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
   const int grid = p.nrt * (S / 8);
   // (the same kernels as the training forward: the GRU front and S = 128 have no bf16-MFMA form)
   if (S == 1024) {
@@ -1303,6 +1344,10 @@ extern "C" int ag_gfront_gen_persist(int cell, const float* pre, const float* w_
 //   both, t > 0    : wait for all dgates_t of the clip tile -> [32 x 4S] x panel on v_mfma_f32_16x16x4_f32 -> LDS sum of
 //                    the 8 K slices -> the recurrent term of frame t-1, kept in a register.
 // Two hand-offs per frame; one slot per frame in dgs / dxt (no parity); flags count frames.
+// Frame sizes below the panel width (fs % 8 == 0, fs <= FS, as in the forward): ceil(fs / 16) x tiles per clip tile, so the
+// grid is ceil(B/32) * (S/16 + ceil(fs/16)); columns at or past fs of the last x tile hold a zero W_x panel and neither load
+// nor store anything; the k lanes of the projection product at or past fs hold zeros on both sides; fs is the row pitch of
+// x, dx_ext and dxt.
 // ------------------------------------------------------------------------------------------
 struct FrontBwdP {
   const float* ga;     // [T,B,4S] activated gates (i, f, g, o)
@@ -1323,18 +1368,20 @@ struct FrontBwdP {
   float* dgh;
   PersistCtl ctl;
   int T, B, ldwx;
+  int fs;              // the real frame size: fs % 8 == 0, 8 <= fs <= FS
 };
 
 template <int S, int FS, bool RB, int CELL = 0>
 __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP p) {
   constexpr int NG = CELL == 1 ? 3 : 4;                     // gate blocks
   constexpr int K4 = NG * S, NU = K4 / 128;                 // 16-k units of the big product per wave
-  constexpr int NHT = S / 16, NXT = FS / 16, NT = NHT + NXT;
+  constexpr int NHT = S / 16;
   constexpr int NP = FS >= 128 ? FS / 128 : 1;              // 16-k units of the projection product per wave
-  static_assert(NU * 128 == K4 && FS % 16 == 0 && S % 16 == 0, "shape");
+  static_assert(NU * 128 == K4 && FS % 16 == 0 && FS / 16 <= 64 && S % 16 == 0, "shape");
   __shared__ float red[8 * 512];
   __shared__ int s_dead;
-  const int T = p.T, B = p.B;
+  const int T = p.T, B = p.B, fs = p.fs;
+  const int NXT = (fs + 15) >> 4, NT = NHT + NXT;           // x tiles / all tiles per clip tile
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   if (tid == 0) s_dead = 0;
@@ -1348,32 +1395,57 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
       const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;       // q < NT / per
       bt = xcd / per;
       ct = (xcd % per) * (NT / per) + q;
+    } else if (per > 0 && per * nbt == 8) {
+      // NT not a multiple of `per` (frame sizes below the panel width, e.g. 77 tiles at fs = 200): the XCD groups do not
+      // hold NT workgroups each.  Slot l of group g takes tile l of clip tile g; the few slots past NT of the larger groups
+      // take, in order, the tiles the smaller groups have no slot for.  A bijection for every grid; all but those few
+      // workgroups of a clip tile still share 8 / nbt XCDs.
+      const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+      const int full = gridDim.x >> 3, rem = gridDim.x & 7;
+      auto cap = [&](int gq) { return per * full + min(max(rem - gq * per, 0), per); };   // workgroups on the XCDs of group gq
+      const int gq = xcd / per, l = (xcd % per) + per * q;
+      if (l < NT) {
+        bt = gq; ct = l;
+      } else {
+        int r = l - NT;
+        for (int g2 = 0; g2 < gq; ++g2) r += max(cap(g2) - NT, 0);
+        for (int g2 = 0; g2 < nbt; ++g2) {
+          const int miss = max(NT - cap(g2), 0);
+          if (r < miss) { bt = g2; ct = cap(g2) + r; break; }
+          r -= miss;
+        }
+      }
     }
   }
   const bool isx = ct >= NHT;
   const int m0 = bt * 32;
   const int n0 = (isx ? ct - NHT : ct) * 16;                // first column inside W_hh / W_x
-  const int64_t BG = (int64_t)B * K4, BH = (int64_t)B * S, BX = (int64_t)B * FS;
+  const int64_t BG = (int64_t)B * K4, BH = (int64_t)B * S, BX = (int64_t)B * fs;
 
   // resident panel: wreg[u][e] = W[(wid*NU + u)*16 + 4g + e][n0 + li]
   float wreg[NU][4];
   {
     const float* W = isx ? p.w_x : p.w_hh;
     const int ldw = isx ? p.ldwx : S;
+    const bool wv = !isx || n0 + li < fs;                   // (x tiles: columns at or past fs are the z/c weights - zeros instead)
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        wreg[u][e] = ag_rbf_if(W[(int64_t)((wid * NU + u) * 16 + 4 * g + e) * ldw + n0 + li], RB);
+        wreg[u][e] = wv ? ag_rbf_if(W[(int64_t)((wid * NU + u) * 16 + 4 * g + e) * ldw + n0 + li], RB) : 0.f;
   }
   // h tiles: wp[u][e] = W_p[(wid*NP + u)*16 + 4g + e][n0 + li]
-  const bool pw_on = !isx && (wid * NP * 16 < FS);
+  // (rows at or past fs lie outside W_p: zeros; a lane's 4 k are all inside or all outside since fs % 4 == 0)
+  const bool pw_on = !isx && (wid * NP * 16 < fs);
   float wp[NP][4];
+  bool pkv[NP];
 #pragma unroll
-  for (int u = 0; u < NP; ++u)
+  for (int u = 0; u < NP; ++u) {
+    pkv[u] = pw_on && (wid * NP + u) * 16 + 4 * g < fs;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      wp[u][e] = pw_on ? ag_rbf_if(p.w_p[(int64_t)((wid * NP + u) * 16 + 4 * g + e) * S + n0 + li], RB) : 0.f;
+      wp[u][e] = pkv[u] ? ag_rbf_if(p.w_p[(int64_t)((wid * NP + u) * 16 + 4 * g + e) * S + n0 + li], RB) : 0.f;
+  }
 
   unsigned* flags_h = p.ctl.hdr + PS_FLAG_OFF + bt * NT;
   unsigned* flags_x = flags_h + NHT;
@@ -1381,7 +1453,7 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
   // epilogue role: thread <-> (clip row, column of the tile)
   const int erow = tid >> 4, ecol = tid & 15;
   const int em = m0 + erow;
-  const bool epi = em < B;
+  const bool epi = em < B && (!isx || n0 + ecol < fs);      // (x tiles: columns at or past fs do not exist)
   // A operand rows of this lane for the two 16-clip halves (clamped: rows past the batch feed only their own, unwritten outputs)
   const int ar0 = min(m0 + li, B - 1), ar1 = min(m0 + 16 + li, B - 1);
   float carry = 0.f, dcn = 0.f, direct = 0.f;
@@ -1391,12 +1463,12 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
     const unsigned seq = (unsigned)(T - t);
     if (isx) {
       if (epi) {
-        const float dx = (p.dx_ext ? p.dx_ext[(int64_t)em * p.lddx + (int64_t)t * FS + n0 + ecol] : 0.f) + carry;
-        const float xv = p.x[(int64_t)em * p.ldx + (int64_t)t * FS + n0 + ecol];
+        const float dx = (p.dx_ext ? p.dx_ext[(int64_t)em * p.lddx + (int64_t)t * fs + n0 + ecol] : 0.f) + carry;
+        const float xv = p.x[(int64_t)em * p.ldx + (int64_t)t * fs + n0 + ecol];
         float gx = dx * (1.f - xv * xv);
         if (s_dead) gx = __builtin_nanf("");
         __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(p.dxt + (int64_t)t * BX, 0, (int)(BX * 4), 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gx), orr, (unsigned)(((int64_t)em * FS + n0 + ecol) * 4), 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gx), orr, (unsigned)(((int64_t)em * fs + n0 + ecol) * 4), 0, 16);
       }
     } else {
       float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, cp = 0.f, cn = 0.f, ext = 0.f;
@@ -1413,7 +1485,7 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
         ext = p.dh_ext ? p.dh_ext[(int64_t)t * BH + (int64_t)em * S + n0 + ecol] : 0.f;
       }
       if (wid == 0 && alive) {
-        alive = ps_wait_flags(p.ctl, flags_x, NXT, seq, lane);
+        alive = ps_wait_flags<true>(p.ctl, flags_x, NXT, seq, lane);
         if (!alive) s_dead = 1;
       }
       __syncthreads();
@@ -1425,8 +1497,13 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
 #pragma unroll
         for (int u = 0; u < NP; ++u) {
           const unsigned ko = (unsigned)(((wid * NP + u) * 16 + 4 * g) * 4);
-          a[0][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar0 * FS * 4) + ko, 0, 16);
-          a[1][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar1 * FS * 4) + ko, 0, 16);
+          a[0][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar0 * fs * 4) + ko, 0, 16);
+          a[1][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar1 * fs * 4) + ko, 0, 16);
+        }
+        if (fs < FS) {     // k at or past fs: the load ran into the next clip's row (or past the buffer: zeros)
+#pragma unroll
+          for (int u = 0; u < NP; ++u)
+            if (!pkv[u]) a[0][u] = a[1][u] = u32x4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int u = 0; u < NP; ++u)
@@ -1526,11 +1603,14 @@ __global__ __launch_bounds__(512) void gfront_persist_bwd_kernel(const FrontBwdP
   }
 }
 
+// workgroups of the backward: per clip tile S/16 h tiles and ceil(fs/16) x tiles
+static int front_bwd_grid(int B, int S, int fs) { return ag_cdiv(B, 32) * (S / 16 + ag_cdiv(fs, 16)); }
+
 static bool front_bwd_shape_ok(int B, int S, int fs, int n_cu) {
-  if (!((S == 1024 && fs == 256) || (S == 128 && fs == 64))) return false;
+  if (!front_fs_ok(S, fs)) return false;
   if (B < 1) return false;
   if (n_cu > 256) n_cu = 256;
-  const int64_t grid = (int64_t)ag_cdiv(B, 32) * ((S + fs) / 16);
+  const int64_t grid = front_bwd_grid(B, S, fs);
   return grid <= n_cu && grid <= (PS_HDR_BYTES / 4 - PS_FLAG_OFF);
 }
 
@@ -1590,9 +1670,9 @@ static int front_bwd_launch(int cell, const float* ga, const float* c_all, const
   p.ga = ga; p.c_all = c_all; p.x = x; p.ldx = ldx; p.dh_ext = dh_ext; p.dx_ext = dx_ext; p.lddx = lddx; p.w_hh = w_hh; p.w_x = w_x; p.w_p = w_p; p.dgs = dgs; p.dxt = dxt;
   p.gh = gh; p.dgh = dgh;
   p.ctl = ps_ctl(ws);
-  p.T = T; p.B = B; p.ldwx = ldwx;
+  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs;
   const bool rb = ag_precision() == AG_PREC_BF16;
-  const int grid = ag_cdiv(B, 32) * ((S + fs) / 16);
+  const int grid = front_bwd_grid(B, S, fs);
   void (*kern)(const FrontBwdP);
   if (cell == 0)
     kern = S == 1024 ? (rb ? gfront_persist_bwd_kernel<1024, 256, true, 0> : gfront_persist_bwd_kernel<1024, 256, false, 0>)

@@ -536,8 +536,11 @@ class GFrontFn(torch.autograd.Function):
             K.col_sum(ds_tb, dws[4 * nl + 3])
             return (None, None) + tuple(front.group.backward(dws))
         dws = front.group.zero_dws() if wg else None
-        fused = (nl == 1 and T > 0 and (S + fs) % 4 == 0
-                 and K.lstm_front_bwd_ok(B, S, fs, x[:, :fs], x[:, :fs]) and K.skinny_ok(gates[0][0], lw[0][1], False))
+        # (the persistent launch takes frame sizes the fused per-frame step does not: any multiple of 8 up to its panel width)
+        fused = nl == 1 and T > 0 and (
+            (wx.stride(1) == 1 and K.gfront_bwd_persist_ok(B, S, fs, dev))
+            or ((S + fs) % 4 == 0 and K.lstm_front_bwd_ok(B, S, fs, x[:, :fs], x[:, :fs])
+                and K.skinny_ok(gates[0][0], lw[0][1], False)))
         if fused:
             dgs, dxt = GFrontFn._bwd_frames_fused(T, B, fs, S, x, dx, ds, gates[0], cs[0], lw[0][1], wx, pw, sw,
                                                   hs[0], dws, nl)

@@ -396,8 +396,11 @@ int ag_lstm_seq_bwd_persist(const float* const* gates, const float* const* whh, 
  * persistent launch with every weight resident in registers (csrc/lstm_persist.hip).  gates [T,B,4S]: in = the z / c
  * part of the gate pre-activations + both biases (one GEMM over all frames), out = activated gates; w_x = W_ih[:, :fs]
  * (row pitch ldwx), w_hh [4S,S], w_p [fs,S], b_p [fs]; outputs hs [T,B,S], cs [T+1,B,S] (cs[0] is written 0 by the launch) and the
- * frames x [B,T*fs].  Supported: (S, fs) in {(1024, 256), (128, 64)}, B <= 64 (ag_gfront_persist_ok); `ws` =
- * ag_gfront_persist_ws_bytes() bytes, used as for ag_lstm_seq_fwd_persist. */
+ * frames x [B,T*fs].  Supported (ag_gfront_persist_ok): S = 1024 with any frame size fs % 8 == 0, 8 <= fs <= 256 (the
+ * reference's default 200 among them), S = 128 with fs % 8 == 0, 8 <= fs <= 64; B <= 64 and ceil(B/32) * S/8 <= n_cu.  The
+ * kernels keep the x panel at the padded width 256 / 64: lanes at or past fs hold zeros, rows of x have the pitch fs.  `ws` =
+ * ag_gfront_persist_ws_bytes() bytes (sized for the padded width: the same for every fs of a state size), used as for
+ * ag_lstm_seq_fwd_persist. */
 int ag_gfront_persist_ok(int B, int S, int fs, int n_cu);
 int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs);
 /* (round 4) x [B,T*fs] has a row pitch `ldx`: the caller may hand over channel 0 of the conv trunk's activation slab, so the
@@ -413,7 +416,8 @@ int ag_gfront_fwd_persist(float* gates, const float* w_x, int ldwx, const float*
  * x [B,T*fs] (row pitch ldx); the external gradients dh_ext [T,B,S] = dL/dh_t (the stop head's) and dx_ext [B,T*fs] =
  * dL/dx_t (the conv trunk's; row pitch lddx - it may be channel 0 of the trunk's gradient slab), each read only and each
  * NULL = zero; w_hh [4S,S], w_x = W_ih[:, :fs] (row pitch ldwx), w_p [fs,S]; outputs dgs [T,B,4S] and dxt [T,B,fs] (d pre-tanh of the projection), which the weight-gradient
- * GEMMs over all frames read.  Supported: (S, fs) as above and ceil(B/32) * (S+fs)/16 <= n_cu (ag_gfront_bwd_persist_ok);
+ * GEMMs over all frames read.  Supported (ag_gfront_bwd_persist_ok): (S, fs) as for ag_gfront_persist_ok and a grid of
+ * ceil(B/32) * (S/16 + ceil(fs/16)) workgroups <= n_cu (154 at B = 64, S = 1024, fs = 200);
  * `ws`: the sticky word + 8 KiB header (see ag_lstm_seq_fwd_persist). */
 int ag_gfront_bwd_persist_ok(int B, int S, int fs, int n_cu);
 int ag_gfront_bwd_persist(const float* ga, const float* c_all, const float* x, int64_t ldx, const float* dh_ext,
@@ -423,7 +427,7 @@ int ag_gfront_bwd_persist(const float* ga, const float* c_all, const float* x, i
 /* The same for the GRU-front generator (BASELINE configs[3]; torch.nn.GRUCell backward, gate order r z n): ga [T,B,3S]
  * activated gates, hs [T+1,B,S] (hs[t] = h_{t-1}, hs[0] = 0) and gh [T,B,3S] (n slot = W_hn h_{t-1} + b_hn) as saved by
  * ag_grufront_fwd_persist; outputs dgi [T,B,3S] (d of the input-side pre-activations), dgh [T,B,3S] (hidden side: the n slot
- * times r) and dxt [T,B,fs].  Shapes and workspace as ag_gfront_bwd_persist. */
+ * times r) and dxt [T,B,fs].  Shapes (any fs % 8 == 0 up to the panel width of S) and workspace as ag_gfront_bwd_persist. */
 int ag_grufront_bwd_persist(const float* ga, const float* hs, const float* gh, const float* x, int64_t ldx,
                             const float* dh_ext, const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x,
                             int ldwx, const float* w_p, float* dgi, float* dgh, float* dxt, void* ws, int64_t ws_bytes, int T,
@@ -433,7 +437,7 @@ int ag_grufront_bwd_persist(const float* ga, const float* hs, const float* gh, c
  * by a GRU cell, gate order r z n as torch.nn.GRUCell) as ONE persistent launch.  gates [T,B,3S]: in = W_ih[:, fs:] zc_t +
  * b_ih + (b_hr, b_hz, 0), out = activated (r, z, n); gh [T,B,3S]: only its n slot is written (W_hn h_{t-1} + b_hn, what
  * ag_gru_cell_bwd reads); w_x = W_ih[:, :fs] (row pitch ldwx), w_hh [3S,S], b_hn [S] = b_hh[2S:], w_p [fs,S], b_p [fs];
- * outputs hs [T,B,S] and the frames x [B,T*fs].  Shapes and workspace as for ag_gfront_fwd_persist. */
+ * outputs hs [T,B,S] and the frames x [B,T*fs].  Shapes (any fs % 8 == 0 up to the panel width of S) and workspace as for ag_gfront_fwd_persist. */
 int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
                             const float* w_p, const float* b_p, float* hs, float* x, int64_t ldx, float* xt, void* ws,
                             int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream);
@@ -448,7 +452,8 @@ int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x, int ldwx,
  * frames clip b generates (1 + its first stop frame, T if it never stops); t_run [1] (int32) = the frames run.  The loop ends
  * early, by one rule every workgroup takes from the same write-once words: before frame t + 1 it reads the decisions of
  * frame t - 1 (a lag of one frame) and leaves iff every clip has stopped by then, so t_run = min(T, max(first) + 1).  Frames
- * past max(first) are correct frames the caller discards.  Shapes and workspace as for ag_gfront_fwd_persist. */
+ * past max(first) are correct frames the caller discards.  Shapes (any fs % 8 == 0 up to the panel width of S: the stop
+ * workgroups are those of column tile 0, which every fs has) and workspace as for ag_gfront_fwd_persist. */
 int ag_gfront_gen_persist(int cell, const float* pre, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
                           const float* w_p, const float* b_p, const float* w_s, const float* b_s, const float* u, float* x,
                           int64_t ldx, float* s, int64_t lds, int* first, int* t_run, void* ws, int64_t ws_bytes, int T, int B,
