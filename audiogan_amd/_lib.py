@@ -49,6 +49,7 @@ SIGNATURES = {
     'ag_flush_reduces': (C.c_int, [vp]),
     'ag_arch': (C.c_char_p, []),
     'ag_last_error': (C.c_char_p, []),
+    'ag_last_kernel': (C.c_char_p, []),
     'ag_weight_norm_fwd': (C.c_int, [vp, C.c_int, C.c_int, vp]),
     'ag_weight_norm_bwd': (C.c_int, [vp, C.c_int, C.c_int, vp]),
     'ag_conv1d_engine': (C.c_int, [C.POINTER(ConvArgs), vp]),
@@ -148,7 +149,7 @@ def _load():
     return lib
 
 
-ABI_VERSION = 11      # what this package was written against (csrc/api.hip: ag_abi_version)
+ABI_VERSION = 12      # what this package was written against (csrc/api.hip: ag_abi_version)
 
 lib = _load()
 if lib.ag_abi_version() != ABI_VERSION:

@@ -1,6 +1,7 @@
 // common.h -- shared device/host helpers for libaudiogan_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -13,6 +14,28 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // last-error text (host side, one per process; the library is driven by one thread per GPU)
 void ag_set_error(const char* fmt, ...);
+
+// ag_last_kernel() (api.hip, per thread): every launch site of a compute kernel that ag_gemm, ag_gemm_h, ag_conv1d_engine
+// or ag_conv1d_wgrad can reach calls ag_note_kernel right before its hipLaunchKernelGGL, with a name built from the
+// template arguments of that very launch.  The name must outlive the call: a literal, or an AgKernelName that is a
+// function-local static of the templated launcher (formatted once per instantiation; a launch costs one pointer store).
+// Second stages (ag_slab_reduce, ag_splitk_reduce) record nothing, so a call is named after its product.  The one place
+// that keeps the rule by save / restore instead of by construction: main_and_tail (conv_engine.hip) puts the main
+// launch's name back after the tail launch of a transposed conv.  gemm_tile.h is also built into tools/gemm_lab.hip,
+// which defines an empty ag_note_kernel of its own.
+void ag_note_kernel(const char* name);
+struct AgKernelName {          // "base<t0,t1,...>": rocprofv3's spelling without spaces
+  char s[96];
+  AgKernelName(const char* base, std::initializer_list<int> targs) {
+    int n = snprintf(s, sizeof(s), "%s", base);
+    char sep = '<';
+    for (int t : targs) {
+      n += snprintf(s + n, sizeof(s) - n, "%c%d", sep, t);
+      sep = ',';
+    }
+    snprintf(s + n, sizeof(s) - n, ">");
+  }
+};
 
 // Two-stage reductions (deterministic: no float atomics).  A caller binds a workspace with ag_bind_workspace() right
 // before a reducing entry point; that entry point takes it (the binding is consumed) and sums partial results in a

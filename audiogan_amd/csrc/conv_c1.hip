@@ -217,6 +217,8 @@ int ag_conv_c1_try_fwd(const ag_conv_args& a, int rb, hipStream_t st, int* rc) {
   if ((((uintptr_t)a.y & 15) != 0) || a.y_bs % 4 != 0 || a.y_cs % 4 != 0) return 0;
   const int opad = ag_roundup(a.O, 32);
   constexpr int OC = 4;
+  static const AgKernelName name("conv_c1_fwd_kernel", {2, 7, OC});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL((conv_c1_fwd_kernel<2, 7, OC>), dim3(ag_cdiv(a.Lout, 1024), a.B, ag_cdiv(a.O, OC)), dim3(256), 0, st, a.x,
                      a.x_bs, a.wp, opad, a.bias, a.y, a.y_bs, a.y_cs, a.lens_i64, a.O, a.Lin, a.Lout, a.pad, a.act, a.slope, rb);
   hipError_t e = hipGetLastError();
@@ -232,6 +234,7 @@ int ag_conv_c1_try_bwdx(const ag_conv_args& a, int rb, hipStream_t st, int* rc) 
   const int mt = ag_cdiv(a.K, a.stride);
   const int aligned = (a.wp_pad == a.pad && ag_scatter_aligned(a.K, a.stride, a.pad)) ? 1 : 0;
   const size_t lds = (size_t)a.C * a.K * sizeof(float);
+  ag_note_kernel("conv_c1_bwdx_kernel<2,7,4>");
   hipLaunchKernelGGL((conv_c1_bwdx_kernel<2, 7, 4>), dim3(ag_cdiv(a.Lin + 3, 1024), a.B), dim3(256), lds, st, a.x, a.x_bs, a.x_cs,
                      a.wp, mt, aligned, a.y, a.y_bs, a.accumulate, a.C, a.Lin, a.Lout, a.pad, rb);
   hipError_t e = hipGetLastError();
@@ -259,6 +262,7 @@ int ag_conv_c1_wgrad(const float* dy, int64_t dy_bs, int64_t dy_cs, const float*
   int bper = 1;
   const int slabs = ag_conv_c1_wgrad_slabs(B, A, Lt, s, K, &bper);
   const int gx = ag_cdiv(Lt, 1024), gz = slabs / gx;
+  ag_note_kernel("conv_c1_wgrad4_kernel<2,7,8>");
   hipLaunchKernelGGL((conv_c1_wgrad4_kernel<2, 7, 8>), dim3(gx, ag_cdiv(A, 8), gz), dim3(256), 0, st, dy, dy_bs, dy_cs, x, x_bs,
                      part, B, A, Lt, Lx, pad, bper, rb);
   AG_CHECK_LAUNCH("ag_conv1d_wgrad(c1)");

@@ -22,10 +22,15 @@ extern "C" int64_t ag_wpb_numel(int d0, int d1, int K, int stride) {
 // The ragged last column(s) of a transposed conv go to a second, narrow-tile launch after the main one.
 // (Running it beside the main launch on a side stream - fork / join events, a parallel branch under graph
 // capture - was measured: slower, both eagerly and in the replayed step.)
+// The tail's launch site records its name like any other; the call stays named after its main launch (ag_last_kernel).
 template <typename MainFn, typename TailFn>
 static int main_and_tail(hipStream_t st, MainFn mainf, TailFn tailf) {
   const int rc = mainf(st);
-  return rc != AG_OK ? rc : tailf(st);
+  if (rc != AG_OK) return rc;
+  const char* main_name = ag_last_kernel();
+  const int rt = tailf(st);
+  ag_note_kernel(main_name);
+  return rt;
 }
 
 extern "C" int ag_conv1d_engine(const ag_conv_args* args, void* stream) {

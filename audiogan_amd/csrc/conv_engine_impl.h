@@ -844,6 +844,8 @@ static int launch_one(ConvP& p, size_t lds, dim3 grid, hipStream_t st) {
   auto kern = conv_engine_kernel<TO, TTL, WO, WT, TAPS, S0>;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static const AgKernelName name("conv_engine_kernel", {TO, TTL, WO, WT, TAPS, S0});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, grid, dim3(p.solo ? 256 : 512), lds, st, p);
   AG_CHECK_LAUNCH("ag_conv1d_engine");
   return AG_OK;
@@ -872,6 +874,8 @@ static int launch_bf16_nw(ConvP& p, hipStream_t st) {
   auto kern = conv_engine_bf16_kernel<TO, TTL, WO, WT, NW>;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static const AgKernelName name("conv_engine_bf16_kernel", {TO, TTL, WO, WT, NW});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, p);
   AG_CHECK_LAUNCH("ag_conv1d_engine(bf16)");
   return AG_OK;

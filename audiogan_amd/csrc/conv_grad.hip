@@ -523,6 +523,8 @@ static int launch_wgrad_bf16(WgP& p, hipStream_t st, AgWs ws) {
   auto kern = conv_wgrad_bf16_kernel<TA, TN, WA, WN>;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static const AgKernelName name("conv_wgrad_bf16_kernel", {TA, TN, WA, WN});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, dim3(gx, gy, gz), dim3(512), lds, st, p);
   AG_CHECK_LAUNCH("ag_conv1d_wgrad(bf16)");
   return ag_slab_reduce(p.part, gz, n_out, p.dw, 1, st);
@@ -558,6 +560,8 @@ static int launch_wgrad(WgP& p, hipStream_t st, AgWs ws) {
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
+  static const AgKernelName name("conv_wgrad_kernel", {TA, TN, WA, WN});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, dim3(gx, gy, gz), dim3(512), lds, st, p);
   AG_CHECK_LAUNCH("ag_conv1d_wgrad");
   return ag_slab_reduce(p.part, gz, n_out, p.dw, 1, st);
@@ -656,6 +660,7 @@ extern "C" int ag_conv1d_wgrad(const float* sh, int64_t sh_bs, int64_t sh_cs, co
     float* part = ws.p;
     const int bper = ag_cdiv(B, gz);
     gz = ag_cdiv(B, bper);
+    ag_note_kernel("conv_c1_wgrad_kernel<8,8>");
     hipLaunchKernelGGL((conv_c1_wgrad_kernel<8, 8>), dim3(gx, gy, gz), dim3(256), 0, st, sh, sh_bs, sh_cs, lg, lg_bs,
                        dw, B, A, Lsh, Llg, K, stride, pad, bper, part, p.rb);
     AG_CHECK_LAUNCH("ag_conv1d_wgrad");

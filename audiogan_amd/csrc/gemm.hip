@@ -504,6 +504,8 @@ static void launch_bf16_one(const GemmP& p, dim3 grid, hipStream_t st) {
   auto kern = gemm_bf16_kernel<TA, TB, X3>;
   const int lds = (X3 ? 128 : 64) * 1024;
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static const AgKernelName name("gemm_bf16_kernel", {TA, TB, X3});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
 }
 
@@ -588,14 +590,21 @@ static int launch_gemm_dma(const GemmP& p, int ta, int tb, hipStream_t st) {
   return AG_OK;
 }
 
+template <int TM, int TN, int WM, int WN, int TA, int TB>
+static void launch_gemm_one(const GemmP& p, dim3 grid, hipStream_t st) {
+  static const AgKernelName name("gemm_kernel", {TM, TN, WM, WN, TA, TB});
+  ag_note_kernel(name.s);
+  hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, TA, TB>), grid, dim3(256), 0, st, p);
+}
+
 template <int TM, int TN, int WM, int WN>
 static int launch_gemm(const GemmP& p, int ta, int tb, hipStream_t st) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   dim3 grid(ag_cdiv(p.N, BN), ag_cdiv(p.M, BM), p.ksplit);
-  if (ta == 0 && tb == 0) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, 0>), grid, dim3(256), 0, st, p);
-  if (ta == 0 && tb == 1) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, 1>), grid, dim3(256), 0, st, p);
-  if (ta == 1 && tb == 0) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, 0>), grid, dim3(256), 0, st, p);
-  if (ta == 1 && tb == 1) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, 1>), grid, dim3(256), 0, st, p);
+  if (ta == 0 && tb == 0) launch_gemm_one<TM, TN, WM, WN, 0, 0>(p, grid, st);
+  if (ta == 0 && tb == 1) launch_gemm_one<TM, TN, WM, WN, 0, 1>(p, grid, st);
+  if (ta == 1 && tb == 0) launch_gemm_one<TM, TN, WM, WN, 1, 0>(p, grid, st);
+  if (ta == 1 && tb == 1) launch_gemm_one<TM, TN, WM, WN, 1, 1>(p, grid, st);
   AG_CHECK_LAUNCH("ag_gemm");
   return AG_OK;
 }

@@ -280,6 +280,8 @@ static void launch_h(const GemmH& p, dim3 grid, hipStream_t st) {
   auto kern = gemm_bf16s_kernel<TA, TB>;
   const int lds = 32 * 1024;          // one stage (2 x 128 x 64 bf16) = the epilogue's [64][128] fp32 image
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static const AgKernelName name("gemm_bf16s_kernel", {TA, TB});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
 }
 

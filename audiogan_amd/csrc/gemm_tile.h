@@ -291,6 +291,8 @@ static inline int gemm_tile_launch_one(const GemmP& p, hipStream_t st) {
     attr = true;
   }
   dim3 grid(ag_cdiv(p.N, BN), ag_cdiv(p.M, BM), p.ksplit);
+  static const AgKernelName name("gemm_tile_kernel", {TA, TB, BM, BN, TI, TJ});
+  ag_note_kernel(name.s);
   hipLaunchKernelGGL(k, grid, dim3(NT), lds, st, p);
   return AG_OK;
 }

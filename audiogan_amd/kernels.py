@@ -86,8 +86,6 @@ def _mat(t, name):
 # ------------------------------------------------------------------------------------
 # two-stage (deterministic) reductions: a per-call workspace bound right before the C call
 # ------------------------------------------------------------------------------------
-import os as _os0
-
 _SMALL_WS = 1 << 17        # floats; enough for the bias / channel / column sums at every BASELINE size
 
 
@@ -740,7 +738,7 @@ def _work_gemm_h(A, B, C=None, C16=None, ta=False, tb=False, *a_, **kw):
     out = C if C is not None else C16
     M, N = out.shape
     Kd = A.size(0) if ta else A.size(1)
-    return 'gemm_bf16s_kernel<%d,%d>' % (int(ta), int(tb)), 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd) + (4.0 if C is not None else 2.0) * M * N
+    return None, 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd) + (4.0 if C is not None else 2.0) * M * N
 
 
 def build_zc(z, c, out=None):
@@ -838,7 +836,7 @@ def opt_step(params, grads, s1, s2, norms, kind, lr, clip, grad_scale, a1, b2, e
 # ------------------------------------------------------------------------------------
 class Profiler(object):
     enabled = False
-    only = None          # kernel-class key to time, or None = every class
+    only = None          # kernel name (as ag_last_kernel / rocprofv3 spell it) or class key to time, or None = all
     records = []         # (key, flops, bytes, ev_start, ev_stop)
 
     @classmethod
@@ -860,101 +858,48 @@ class Profiler(object):
         return out
 
 
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
 def _bf16_tag():
     """bf16 mode: the persistent recurrent kernels run their v_mfma_f32_*_bf16 instantiation"""
     return '<bf16>' if lib.ag_get_precision() == 1 else ''
 
 
+# _work_*(same arguments as the wrapped call) -> (key, flops, bytes[, launches]): the algorithmic work of the call from its
+# shapes.  key None: the library chose among kernel forms and names the one it launched itself (ag_last_kernel).
 def _work_gemm(A, B, Cm, ta=False, tb=False, *a_, **kw):
     M, N = Cm.shape
     Kd = A.size(0) if ta else A.size(1)
-    big = _cdiv(M, 128) * _cdiv(N, 128)
-    use128 = M > 64 and N > 64 and (big >= 192 or Kd >= 2048)
-    # mirrors ag_gemm's dispatch: the LDS-DMA kernel takes the 128x128 case when K % 16 == 0 and rows are 16-B aligned
-    dma = use128 and Kd % 16 == 0 and (not ta or M % 4 == 0) and (tb or N % 4 == 0) and \
-        A.stride(0) % 4 == 0 and B.stride(0) % 4 == 0 and _al16(A) and _al16(B)
-    bf_shape_ok = (M > 32 and N > 32 and Kd % 4 == 0 and A.stride(0) % 4 == 0 and
-                   B.stride(0) % 4 == 0 and _al16(A) and _al16(B) and (not ta or M % 4 == 0) and (tb or N % 4 == 0))
-    bf = lib.ag_get_precision() == 1 and bf_shape_ok
-    x3 = lib.ag_get_precision() == 2 and use128 and bf_shape_ok
-    if bf or x3:
-        key = 'gemm_bf16_kernel<%d,%d%s>' % (int(ta), int(tb), ',x3' if x3 else '')
-    elif dma:
-        # mirrors gemm_pick_tile (gemm.hip): the largest tile that still gives every CU a workgroup
-        act = kw.get('act', ACT_NONE)
-        ks = 1
-        wsn = int(lib.ag_gemm_ws_numel(M, N, Kd, int(act)))
-        if wsn:
-            kchunk = _cdiv(_cdiv(Kd, wsn // (M * N)), 64) * 64
-            ks = _cdiv(Kd, kchunk)
-        best, best_t = None, 0.0
-        for (bm, bn, ti, tj), rate in (((256, 256, 2, 4), 137.), ((256, 128, 2, 2), 133.), ((128, 256, 2, 2), 133.),
-                                       ((128, 128, 2, 2), 120.)):
-            wgs = _cdiv(M, bm) * _cdiv(N, bn) * ks
-            t = _cdiv(wgs, 256) * bm * bn / rate + 1e-9 * wgs * bm * bn
-            if best is None or t < best_t * 0.98:
-                best, best_t = (bm, bn, ti, tj), t
-        key = 'gemm_tile_kernel<%d,%d,%d,%d,%d,%d>' % ((int(ta), int(tb)) + best)
-    else:
-        key = 'gemm_kernel<%s,%d,%d>' % ('2,2,2,2' if use128 else '1,1,2,2', int(ta), int(tb))
-    return key, 2.0 * M * N * Kd, 4.0 * (M * Kd + N * Kd + M * N)
+    return None, 2.0 * M * N * Kd, 4.0 * (M * Kd + N * Kd + M * N)
 
 
 def _work_conv(x, wp, y, K_, stride, pad, mode, *a_, **kw):
     B, Cc, Lin = x.shape
     _, O, Lout = y.shape
-    rows = O if mode == 0 else O * stride
-    ncnt = Lout if mode == 0 else _cdiv(Lout, stride)
-    if rows <= 32:
-        tile = '1,2,1,4'
-    elif rows <= 64:
-        tile = '2,1,1,4'
-    elif ncnt <= 64:
-        tile = '2,1,2,2'
-    else:
-        tile = '2,2,2,2'
-    if mode == 1 and _cdiv(K_, stride) == 2 and rows > 64 and lib.ag_get_precision() != 1:
-        tile = '2,1,2,2'         # (conv_engine.hip: two tap slots take 128 x 64 tiles)
     macs = B * O * Lout * Cc * K_ if mode == 0 else B * Cc * Lin * O * K_
-    if (K_, stride) == (7, 2) and _os0.environ.get('AG_CONV_C1', '1') != '0':
-        # the critic's single-input-channel first layer and its backward-data: streaming kernels (conv_c1.hip)
-        if mode == 0 and Cc == 1 and kw.get('res') is None and not kw.get('accumulate'):
-            return 'conv_c1_fwd_kernel<%d,%d>' % (stride, K_), 2.0 * macs, 4.0 * (x.numel() + y.numel() + O * K_)
-        if mode == 1 and O == 1 and kw.get('res') is None and kw.get('bias') is None and kw.get('lens') is None:
-            return 'conv_c1_bwdx_kernel<%d,%d>' % (stride, K_), 2.0 * macs, 4.0 * (x.numel() + y.numel() + Cc * K_)
-    taps = K_ if mode == 0 else _cdiv(K_, stride)
-    ts = (taps, stride if mode == 0 else 0)
-    if ts not in ((17, 8), (9, 4), (7, 2), (3, 1), (16, 8), (8, 4), (2, 0), (3, 0), (4, 0)):
-        ts = (0, 0)
-    nbytes = 4.0 * (x.numel() + y.numel() + O * Cc * K_)
-    if lib.ag_get_precision() == 1 and Cc >= 16 and Lin % 4 == 0:
-        # mirrors launch_bf16 (conv_engine.hip): the bf16-MFMA kernel takes the launch when a chunk's staging fits
-        ot = {'1,2,1,4': 32, '2,1,1,4': 64, '2,1,2,2': 128, '2,2,2,2': 128}[tile]
-        tt = {'1,2,1,4': 256, '2,1,1,4': 128, '2,1,2,2': 64, '2,2,2,2': 128}[tile]
-        sp = stride if mode == 0 else 1
-        ncols = tt + ((K_ - 1) // stride if mode == 0 else taps - 1)
-        nq = (sp * ncols + 6) // 4 + 1
-        deep = ot >= 128 and (-(-Cc // 16)) * taps >= 32
-        if 2 * nq <= 512 and taps * 2 * ot <= (16 if deep else 8) * 256:
-            return 'conv_engine_bf16_kernel<%s>' % tile, 2.0 * macs, nbytes
-    return 'conv_engine_kernel<%s,%d,%d>' % (tile, ts[0], ts[1]), 2.0 * macs, nbytes
+    return None, 2.0 * macs, 4.0 * (x.numel() + y.numel() + O * Cc * K_)
 
 
 def _work_wgrad(sh, lg, dw, K_, stride, pad):
     B, A, Lsh = sh.shape
     Cc = lg.size(1)
-    if Cc == 1 and (K_, stride) == (7, 2) and _os0.environ.get('AG_CONV_C1', '1') != '0':
-        return 'conv_c1_wgrad4_kernel<%d,%d>' % (stride, K_), 2.0 * B * A * Lsh * K_, 4.0 * (sh.numel() + lg.numel() + dw.numel())
-    tile = '1,1,1,4' if A <= 32 else ('1,1,2,2' if (A <= 64 or Cc * K_ <= 64) else '2,2,2,2')
-    return 'conv_wgrad_kernel<%s>' % tile, 2.0 * B * A * Lsh * Cc * K_, 4.0 * (sh.numel() + lg.numel() + dw.numel())
+    return None, 2.0 * B * A * Lsh * Cc * K_, 4.0 * (sh.numel() + lg.numel() + dw.numel())
+
+
+def _call_sig(a, k):
+    """everything about a call that a dispatch rule could look at, without knowing any rule: per argument a tensor's shape,
+    strides, dtype and alignment, a list element by element, anything else by value; plus the precision mode.  The result
+    is a dict key: every other argument must be hashable (numbers, bools, None, strings - all the four naming wrappers take)"""
+    def one(v):
+        if isinstance(v, torch.Tensor):
+            return tuple(v.shape), v.stride(), v.dtype, v.data_ptr() % 16
+        if isinstance(v, (list, tuple)):
+            return tuple(one(e) for e in v)
+        return v
+    return tuple(one(v) for v in a), tuple((n, one(k[n])) for n in sorted(k)), lib.ag_get_precision()
 
 
 def _instrument(name, work):
     fn = globals()[name]
+    seen = {}       # call signature -> the kernel name the library reported for it last time (only steers `only`)
 
     def wrapped(*a, **k):
         if not Profiler.enabled:
@@ -962,12 +907,19 @@ def _instrument(name, work):
         w_ = work(*a, **k) if work is not None else (name, 0.0, 0.0)
         key, fl, by = w_[:3]
         nl = w_[3] if len(w_) > 3 else 1        # launches behind this call (a whole recurrent layer pass: T)
-        if Profiler.only is not None and key != Profiler.only:
+        only = Profiler.only
+        if key is None:
+            sig = _call_sig(a, k)
+            if only is not None and seen.get(sig, only) != only:     # (a signature not seen yet is timed and learnt)
+                return fn(*a, **k)
+        elif only is not None and key != only:
             return fn(*a, **k)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         r = fn(*a, **k)
         e1.record()
+        if key is None:
+            key = seen[sig] = lib.ag_last_kernel().decode()
         Profiler.records.append((key, fl, by, e0, e1, nl))
         return r
     wrapped.__name__ = name

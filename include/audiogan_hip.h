@@ -43,6 +43,16 @@ extern "C" {
 int ag_abi_version(void);
 const char* ag_arch(void);
 const char* ag_last_error(void);
+/* Name of the compute kernel that the calling thread's most recent call to ag_gemm, ag_gemm_h, ag_conv1d_engine or
+ * ag_conv1d_wgrad (the entry points that choose among kernel forms) launched, as rocprofv3 spells it without the leading
+ * "void ", the parameter list and spaces: "conv_engine_kernel<2,1,2,2,7,2>", "gemm_bf16_kernel<0,1,0>".  "" before the
+ * first such call on this thread; a call that fails before its launch leaves the previous name.  Per thread, like
+ * ag_last_error: read it on the thread that made the call (backward calls come from the autograd thread).
+ * The name is recorded at the launch site itself, from the template arguments of the launch.  A call with several launches
+ * is named after its main product: second stages (the slab / split-K reduces) record no name, and a transposed conv that
+ * adds a tail launch for its ragged last columns puts the main launch's name back after the tail.  The string is static
+ * storage owned by the library. */
+const char* ag_last_kernel(void);
 
 /* ---------------------------------------------------------------------------
  * Weight norm  (audiogan.py:77-80; torch.nn.utils.weight_norm, dim 0)
