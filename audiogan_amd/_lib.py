@@ -39,6 +39,14 @@ class OptDesc(C.Structure):
     _fields_ = [('p', vp), ('grad', vp), ('s1', vp), ('s2', vp), ('n', i64)]
 
 
+SUMMARY_COLS = 16
+
+
+class SummaryDesc(C.Structure):
+    _fields_ = [('src', vp * SUMMARY_COLS), ('imm', C.c_uint32 * SUMMARY_COLS), ('part', vp), ('ring', vp), ('cursor', vp),
+                ('npart', i32), ('part_col', i32), ('capacity', i32), ('pad_', i32)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/audiogan_hip.h
 SIGNATURES = {
     'ag_abi_version': (C.c_int, []),
@@ -133,6 +141,10 @@ SIGNATURES = {
     'ag_axpby': (C.c_int, [vp, vp, i64, f32, f32, vp]),
     'ag_grad_norms': (C.c_int, [vp, C.c_int, vp, vp, vp, f32, vp, C.c_int, vp]),
     'ag_opt_step': (C.c_int, [vp, C.c_int, vp, C.c_int, f32, f32, f32, f32, f32, f32, C.c_int, vp, vp, vp, vp, vp, vp]),
+    'ag_logit_summary': (C.c_int, [vp, i64, i64, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
+    'ag_sqnorm_rows': (C.c_int, [vp, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
+    'ag_vec_stats': (C.c_int, [vp, f32, vp, C.c_int, vp]),
+    'ag_summary_commit': (C.c_int, [vp, vp]),
 }
 
 

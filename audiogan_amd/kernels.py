@@ -1080,8 +1080,12 @@ def check_persist_status(dev=None):
     st = lstm_persist_status(dev)
     if st:
         lstm_persist_status(dev, reset=True)
-        raise PersistentLaunchError(
-            'audiogan_amd: a persistent recurrent launch timed out waiting for its group (status 0x%08x: step %d); its '
+        raise PersistentLaunchError(persist_error_text(st))
+
+
+def persist_error_text(st):
+    """what ``check_persist_status`` says about a non-zero sticky word (summary.Summary.drain raises the same)"""
+    return ('audiogan_amd: a persistent recurrent launch timed out waiting for its group (status 0x%08x: step %d); its '
             'workgroups were not all co-resident - is another persistent or collective kernel holding compute units? '
             'Results of that launch are NaN.  AG_LSTM_PERSIST=0 selects the per-step kernels.' % (st, st & 0x7FFFFFFF))
 
@@ -1689,3 +1693,111 @@ def layer_norm_hbfw_bwd(dy, x, gamma, mean, rstd, dx, dgp, dbp):
 for _n in ('convlstm_peephole_fwd', 'convlstm_peephole_bwd', 'convlstm_cell_fwd', 'convlstm_cell_bwd', 'convlstm_out_fwd',
            'convlstm_out_bwd', 'layer_norm_hbfw_fwd', 'layer_norm_hbfw_bwd'):
     _instrument(_n, None)
+
+
+# ------------------------------------------------------------------------------------
+# per-iteration summaries (audiogan.py:776-809, :875-884, :911-920) as device scalars + the ring row that gathers them
+# ------------------------------------------------------------------------------------
+SUMMARY_COLS = _lib.SUMMARY_COLS
+
+
+def _small_out(out, n, dev, name):
+    if out is None:
+        return torch.empty(n, dtype=torch.float32, device=dev)
+    _chk(out, name)
+    assert out.is_contiguous() and out.numel() == n, (name, tuple(out.shape))
+    return out
+
+
+def logit_summary(cls, nframes, positive, out=None):
+    """one critic output cls [B,T'] (fp32, any strides: ``Discriminator.classify`` returns a transposed view) ->
+    out [5] = (mean, std, hits, mask sum, hits / mask sum): mean / std over all B*T' entries, population (numpy's
+    ``.mean()`` / ``.std()``, audiogan.py:799-802); hits = entries inside ``nframes`` with cls > 0 (``positive``) or < 0
+    (ag_logit_summary: one launch, two-pass variance, fixed-order sums)"""
+    _chk(cls, 'cls'); _chk(nframes, 'nframes', torch.int64)
+    assert cls.dim() == 2, tuple(cls.shape)
+    B, T = cls.shape
+    assert nframes is None or (nframes.is_contiguous() and nframes.numel() == B)
+    out = _small_out(out, 5, cls.device, 'out')
+    check(lib.ag_logit_summary(_p(cls), cls.stride(0), cls.stride(1), _p(nframes), int(bool(positive)), _p(out), B, T,
+                               _stream()), 'ag_logit_summary')
+    return out
+
+
+def sqnorm_rows(gx, nframes, scale, part=None, out=None, finish=True):
+    """gx [B,L] (unit stride along L, any row pitch; 16-byte aligned rows are read four at a time) ->
+    part[b] = scale * sum_l gx[b,l]^2 / nframes[b].  ``finish``: a second launch writes out[0] = mean_b part[b] (b ascending);
+    False: the caller hands ``part`` to ``summary_commit``, which takes the same mean.  Returns (part, out or None)."""
+    B, L = gx.shape
+    ld = _rows(gx, 'gx', B, L)
+    _chk(nframes, 'nframes', torch.int64)
+    assert nframes is None or (nframes.is_contiguous() and nframes.numel() == B)
+    part = _small_out(part, B, gx.device, 'part')
+    if finish:
+        out = _small_out(out, 1, gx.device, 'out')
+    else:
+        assert out is None
+    check(lib.ag_sqnorm_rows(_p(gx), ld, _p(nframes), float(scale), _p(part), _p(out), B, L, _stream()), 'ag_sqnorm_rows')
+    return part, out
+
+
+def vec_stats(v, sign=1.0, out=None):
+    """v [n] contiguous -> out [2] = (sign * mean(v), population std(v)) (ag_vec_stats; reward/mean, reward/std of :879-880)"""
+    _chk(v, 'v')
+    assert v.dim() == 1 and v.is_contiguous() and v.numel() > 0, tuple(v.shape)
+    out = _small_out(out, 2, v.device, 'out')
+    check(lib.ag_vec_stats(_p(v), float(sign), _p(out), v.numel(), _stream()), 'ag_vec_stats')
+    return out
+
+
+def persist_status_word(dev):
+    """the sticky status word of the CURRENT persistent workspace on ``dev`` as an int32 [1] view (None: no persistent
+    launch has run there yet)"""
+    dev = torch.device(dev)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    lst = _persist_ws.get(dev, [])
+    return lst[0][:4].view(torch.int32) if lst else None
+
+
+def summary_commit(ring, cursor, cols, part=None, part_col=-1):
+    """one row of the summary ring in one launch (ag_summary_commit).  ring: int32 [capacity, 16] contiguous; cursor: int32
+    [2] (next row, next sequence number; both advanced by the launch); cols: 16 entries, each a one-element float32 / int32
+    device tensor (its 32-bit word is copied as it is), a Python int (int32 bits), a float (fp32 bits) or None (0) - column
+    1 is overwritten by the sequence number; part / part_col: column ``part_col`` = mean of the fp32 vector ``part`` (b
+    ascending, what ``sqnorm_rows(finish=True)`` computes).  The descriptor goes through the table arena: a captured launch
+    keeps reading its device copy on every replay."""
+    import struct
+    _chk(ring, 'ring', torch.int32); _chk(cursor, 'cursor', torch.int32); _chk(part, 'part')
+    assert ring.dim() == 2 and ring.size(1) == SUMMARY_COLS and ring.is_contiguous() and ring.size(0) >= 1
+    assert cursor.is_contiguous() and cursor.numel() == 2 and len(cols) == SUMMARY_COLS
+    d = _lib.SummaryDesc()
+    for i, c in enumerate(cols):
+        if torch.is_tensor(c):
+            if not c.is_cuda:
+                raise RuntimeError('audiogan_amd: summary column %d must be a CUDA (HIP) tensor; there is no CPU path' % i)
+            if c.dtype not in (torch.float32, torch.int32) or c.numel() != 1:
+                raise TypeError('audiogan_amd: summary column %d must be one float32 / int32 element, got %s %r'
+                                % (i, c.dtype, tuple(c.shape)))
+            d.src[i] = c.data_ptr()
+        elif isinstance(c, float):
+            d.imm[i] = struct.unpack('<I', struct.pack('<f', c))[0]
+        elif c is not None:
+            d.imm[i] = int(c) & 0xFFFFFFFF
+    if part is not None:
+        assert part.is_contiguous() and part.dim() == 1 and 0 <= part_col < SUMMARY_COLS
+        d.part, d.npart, d.part_col = part.data_ptr(), part.numel(), int(part_col)
+    else:
+        d.part_col = -1
+    d.ring, d.cursor, d.capacity = ring.data_ptr(), cursor.data_ptr(), ring.size(0)
+    tab = _table('summary', [d], ring.device)
+    check(lib.ag_summary_commit(_p(tab), _stream()), 'ag_summary_commit')
+
+
+def _work_named(*a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    return None, 0.0, 0.0
+
+
+for _n in ('logit_summary', 'sqnorm_rows', 'vec_stats', 'summary_commit'):
+    _instrument(_n, _work_named)

@@ -25,7 +25,13 @@ iteration.  ~3000 launches per pass are then paced by the GPU, not by the Python
 Samples (:922-935): with ``sample_every`` > 0, every ``sample_every``-th generator iteration is followed by an eager
 ``Generator.generate`` from fixed words and a fixed z, in eager and graphed loops alike; its stop draws come from a private
 ``torch.Generator``, so sampling changes no training bit.  ``sample_dir``: every ``audio_every``-th generator iteration the
-samples are also written as WAV files (audio.write_wav), each cut to its clip's length."""
+samples are also written as WAV files (audio.write_wav), each cut to its clip's length.
+
+Summaries (:776-809, :875-884, :911-920): with ``summary=summary.Summary(...)`` every executed iteration - eager, replayed, or
+one of the eager warm-up iterations of a capture - commits the reference's scalars to a row of the summary's device ring (no
+host read: a captured loop logs like an eager one).  The loop drains the ring every ``summary_every`` iterations, at the end of
+``run()`` and before every checkpoint; a drain raises on NaN / |g| > 1e5 gradients and on a persistent launch that gave up
+(``check_grad``, :786, :909), so a bad run stops and its state is never saved."""
 import os
 import time
 
@@ -40,7 +46,7 @@ class TrainLoop(object):
                  critic_iter=100, require_acc=0.5, gencatchup=1, dgradclip=1.0, ggradclip=0.1, g_optim='boundary_seeking',
                  checkpoint_every=500, checkpoint_prefix=None, fixed_critic_iter=None, stop=None, check=True, graphed=False,
                  host=None, sample_every=0, sample_words=None, sample_z=None, sample_seed=0, on_sample=None, sample_dir=None,
-                 audio_every=500):
+                 audio_every=500, summary=None, summary_every=None):
         """``loader``: the generator ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths, keys, cseq,
         clen], dataset.py:91); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
         (``dataset.pick_words(..., skip_samples=True)[1:3]``, audiogan.py:715-716); ``stop``: None = Bernoulli stop draws
@@ -53,7 +59,10 @@ class TrainLoop(object):
         ``sample_z``: the fixed [batch_size, T, noise] z (default: drawn once from ``sample_seed``); ``on_sample(gen_iter, wave,
         length, stop_list)``: receives every sample; ``sample_dir`` / ``audio_every``: write the samples of every
         ``audio_every``-th generator iteration to ``<sample_dir>/sample-<gen_iter>-<i>.wav``.  The uniforms of the last sample's
-        stop draws are kept in ``last_sample_u``."""
+        stop draws are kept in ``last_sample_u``.
+
+        ``summary``: a ``summary.Summary`` that receives one row per executed iteration (None: no iteration launches or logs
+        anything more than before); ``summary_every``: drain it every so many iterations (default: half its capacity)."""
         self.g, self.d, self.e_g, self.e_d, self.opt_g, self.opt_d = g, d, e_g, e_d, opt_g, opt_d
         self.loader, self.pick_words = loader, pick_words
         self.B, self.maxlen, self.dev = batch_size, maxlen, torch.device(device)
@@ -62,6 +71,9 @@ class TrainLoop(object):
         self.checkpoint_every, self.prefix = checkpoint_every, checkpoint_prefix
         self.fixed_critic_iter, self.stop, self.check = fixed_critic_iter, stop, check
         self.dis_iter = self.gen_iter = 0
+        self.summary = summary
+        self.summary_every = None if summary is None else max(1, int(summary_every or max(1, summary.capacity // 2)))
+        self._since_drain = 0
         self.baseline = None
         self.log = []
         fs = g._frame_size
@@ -167,13 +179,13 @@ class TrainLoop(object):
                 self._out['d%d' % parity] = train.d_step_full(
                     self.g, self.d, self.e_g, self.e_d, self.opt_d, 2 if even else 1, st['real'], st['real_len'], st['lcs'],
                     st['lcl'], st['wcs'], st['wcl'], st['z'], st['n1'] if even else None, st['n2'] if even else None,
-                    self.dgradclip, stop='never', check=False, host=False)
+                    self.dgradclip, stop='never', check=False, host=False, **self._summary_kw())
             return body
 
         def g_body():
             r = train.g_step_full(self.g, self.d, self.e_g, self.e_d, self.opt_g, st['real'], st['real_len'], st['wcs'], st['wcl'],
                                   st['z'], st['n1'], st['n2'], st['n3'], 'never', 'never', st['baseline'], self.ggradclip,
-                                  self.g_optim, check=False, host=False)
+                                  self.g_optim, check=False, host=False, **self._summary_kw())
             st['baseline'].copy_(r['baseline'])           # the running baseline lives on the device, updated by the graph
             self._out['g'] = r
 
@@ -253,6 +265,22 @@ class TrainLoop(object):
                 write_wav(os.path.join(self.sample_dir, 'sample-%05d-%d.wav' % (n, i)), w[i, :int(ln[i])])
         return wave, length, stop_list
 
+    # ---- summaries ------------------------------------------------------------------------
+    def _summary_kw(self, **kw):
+        """the iterations' extra arguments (none without a summary: the calls are then exactly what they were)"""
+        return dict(summary=self.summary, **kw) if self.summary is not None else {}
+
+    def drain_summary(self):
+        """read the rows committed so far (``Summary.drain``: raises if one of them reports a bad iteration)"""
+        self._since_drain = 0
+        return self.summary.drain() if self.summary is not None else []
+
+    def _summary_tick(self):
+        if self.summary is not None:
+            self._since_drain += 1
+            if self._since_drain >= self.summary_every:
+                self.drain_summary()
+
     # ---- iterations -----------------------------------------------------------------------
     def d_iteration(self):
         if self.graphed:
@@ -261,7 +289,10 @@ class TrainLoop(object):
             self.dis_iter += 1
             even = self.dis_iter % 2 == 0
             self._next_inputs(2 if even else 0)
+            if self.summary is not None:
+                self.summary.expect(0, self.dis_iter)          # (the replay commits the row)
             self._replay('d0' if even else 'd1')
+            self._summary_tick()
             return self._out['d0' if even else 'd1']
         self.dis_iter += 1
         real, real_len, cs, cl = self._real()
@@ -270,11 +301,13 @@ class TrainLoop(object):
         even = self.dis_iter % 2 == 0       # (odd iterations take the FGSM branch: no instance noise is drawn, :729-736, :752-759)
         r = train.d_step_full(self.g, self.d, self.e_g, self.e_d, self.opt_d, self.dis_iter, real, real_len, cs, cl, cs2, cl2, z,
                               self._noise() if even else None, self._noise() if even else None, self.dgradclip,
-                              stop=self._stop_arg(self.nframes), check=self.check, host=self.host)
+                              stop=self._stop_arg(self.nframes), check=self.check, host=self.host, **self._summary_kw())
+        self._summary_tick()
         return r
 
     def _maybe_checkpoint(self):
         if self.prefix is not None and self.checkpoint_every and self.gen_iter % self.checkpoint_every == 0:
+            self.drain_summary()           # (raises on a bad iteration: its state is not saved)
             b = self.baseline
             checkpoint.save(self.prefix, self.gen_iter, d=self.d, g=self.g, e_g=self.e_g, e_d=self.e_d, opt_d=self.opt_d,
                             opt_g=self.opt_g, extra=dict(dis_iter=self.dis_iter, gen_iter=self.gen_iter,
@@ -286,8 +319,11 @@ class TrainLoop(object):
                 self._capture()
             self.gen_iter += 1
             self._next_inputs(3)
+            if self.summary is not None:
+                self.summary.expect(1, self.gen_iter)
             self._replay('g')
             self.baseline = self._static['baseline']
+            self._summary_tick()
             self._maybe_checkpoint()
             self._maybe_sample()
             return self._out['g']
@@ -297,8 +333,10 @@ class TrainLoop(object):
         z0 = torch.randn(self.B, self.nframes, self.g._noise_size, device=self.dev)
         r = train.g_step_full(self.g, self.d, self.e_g, self.e_d, self.opt_g, real, real_len, cs, cl, z0, self._noise(),
                               self._noise(), self._noise(), self._stop_arg(self.nframes), self._stop_arg(self.nframes),
-                              self.baseline, self.ggradclip, self.g_optim, check=self.check, host=self.host)
+                              self.baseline, self.ggradclip, self.g_optim, check=self.check, host=self.host,
+                              **self._summary_kw(gen_iter=self.gen_iter))
         self.baseline = r['baseline']
+        self._summary_tick()
         self._maybe_checkpoint()
         self._maybe_sample()
         return r
@@ -327,6 +365,7 @@ class TrainLoop(object):
     def run(self, n_outer):
         for _ in range(n_outer):
             self.outer()
+        self.drain_summary()
         return self.log
 
     def resume(self, iteration):

@@ -236,14 +236,19 @@ def _acc(cls, nframes, positive, host=True):
 
 
 def d_step_full(g, d, e_g, e_d, opt_d, dis_iter, real, real_len, cs, cl, cs2, cl2, z, noise_real, noise_fake,
-                dgradclip=1.0, stop=None, check=True, host=True):
+                dgradclip=1.0, stop=None, check=True, host=True, summary=None):
     """critic iteration ``dis_iter`` of audiogan.py:706-788.  Even iterations: instance noise on the real and the
     generated clips (:724-728, :749-751).  Odd iterations: clean real clips (the FGSM perturbation of :735-736 is
     computed after ``cls_d`` and never reaches the loss, so it is not computed here) and generated clips moved by
     +-1e-3 along the sign of the critic's input gradient (:752-759, ``extras.adversarial_movement_d``: an
     input-gradient pass that leaves every ``.grad`` untouched).  ``opt_d`` holds the parameters of d and e_d (:691).
     ``host=False``: the accuracies stay device scalars - with ``check=False`` and ``stop='never'`` the iteration then issues no
-    host read at all and can be captured into a hipGraph (loop.TrainLoop(graphed=True))."""
+    host read at all and can be captured into a hipGraph (loop.TrainLoop(graphed=True)).
+    ``summary`` (a ``summary.Summary``): the reference's scalars of :776-809 go into one row of its ring - the final
+    generated clips get ``requires_grad`` (:760), so the backward leaves ``fake.grad`` (one more backward-data pass of the
+    critic's first layer; returned as ``x_grad``), from which ``x_grad_norm`` follows: ``loss_d`` does not depend on the
+    clips and the critic has no cross-sample op, so the reference's autograd.grad(loss_g per sample, fake, ones) (:769-775)
+    is B * fake.grad.  No host read and no random draw is added."""
     even = dis_iter % 2 == 0
     embed_real = e_d(cs, cl)
     cls_d, _, _, nf_d = d(real + noise_real if even else real, real_len, embed_real)
@@ -256,25 +261,39 @@ def d_step_full(g, d, e_g, e_d, opt_d, dis_iter, real, real_len, cs, cl, cs2, cl
         fake = fake + noise_fake[:, :fake.size(1)]
     else:
         fake = fake + adversarial_movement_d(fake, fake_len, embed_d.detach(), 0.0, None, d, scale=1e-3)
+    if summary is not None:
+        fake = fake.detach().requires_grad_(True)
     cls_g, _, _, nf_g = d(fake, fake_len, embed_d)
     loss_g, _ = masked_bce_mean(cls_g, 0.0, nf_g.contiguous())
     loss = loss_d + loss_g
     opt_d.zero_grad()
     _backward(loss)
     opt_d.step(clip_norm=dgradclip, check=check)
-    return dict(loss=loss.detach(), loss_d=loss_d.detach(), loss_g=loss_g.detach(), cls_d=cls_d.detach(),
-                cls_g=cls_g.detach(), grad_norm=opt_d.last_norm_sum,
-                acc_d=_acc(cls_d.detach(), nf_d, True, host), acc_g=_acc(cls_g.detach(), nf_g, False, host))
+    r = dict(loss=loss.detach(), loss_d=loss_d.detach(), loss_g=loss_g.detach(), cls_d=cls_d.detach(),
+             cls_g=cls_g.detach(), grad_norm=opt_d.last_norm_sum,
+             acc_d=_acc(cls_d.detach(), nf_d, True, host), acc_g=_acc(cls_g.detach(), nf_g, False, host))
+    if summary is not None:
+        B = fake.size(0)
+        sd = K.logit_summary(r['cls_d'], nf_d.contiguous(), True, out=summary.stat_d)
+        sg = K.logit_summary(r['cls_g'], nf_g.contiguous(), False, out=summary.stat_g)
+        part, _ = K.sqnorm_rows(fake.grad, nf_g.contiguous(), float(B) * B, part=summary.part(B), finish=False)
+        summary.commit(0, dis_iter, {2: r['loss_d'], 3: r['loss_g'], 4: r['loss'], 5: sd[0:1], 6: sd[1:2], 7: sg[0:1],
+                                     8: sg[1:2], 9: sd[4:5], 10: sg[4:5], 11: opt_d.last_norm_sum, 13: opt_d.last_flags},
+                       part=part, part_col=12)
+        r['x_grad'], r['nf_d'], r['nf_g'] = fake.grad, nf_d, nf_g          # (for tests: what the row was computed from)
+    return r
 
 
 def g_step_full(g, d, e_g, e_d, opt_g, real, real_len, cs, cl, z0, noise_real, noise_adv, noise_fake, stop_adv, stop,
-                baseline=None, ggradclip=0.1, g_optim='boundary_seeking', lambda_fp=1.0, check=True, host=True):
+                baseline=None, ggradclip=0.1, g_optim='boundary_seeking', lambda_fp=1.0, check=True, host=True, summary=None,
+                gen_iter=None):
     """generator iteration of audiogan.py:816-921: adversarial z (:836), generator + critic forward (:841-847), feature
     penalty against the critic's statistics on the real clips (:847-855), BCE towards 0.5 (:857-864), reward / baseline
     (:873-887), loss + penalty (:897), REINFORCE of the stop draws into the stop head only (:898-908), per-parameter clip
     and step over the parameters of g and e_g (:909-921).  Returns a dict with the new ``baseline``.  ``baseline``: None (first
     iteration), a float, or a device scalar; ``host=False``: it is kept / returned as a device scalar (no host read: the
-    iteration can be captured into a hipGraph, see d_step_full)."""
+    iteration can be captured into a hipGraph, see d_step_full).  ``summary``: the scalars of :875-884, :911-920 and :940 go
+    into one row of its ring, filed under generator iteration ``gen_iter`` (None: the rows are counted)."""
     B = real.size(0)
     fs, ns = g._frame_size, g._noise_size
     embed_g = e_g(cs, cl)
@@ -290,6 +309,9 @@ def g_step_full(g, d, e_g, e_d, opt_g, real, real_len, cs, cl, z0, noise_real, n
         pen = feature_penalty_fused(hs_d, hl_d, hs_g, hl_g, B)
         bce, per = masked_bce_mean(cls_g, 0.5 if g_optim == 'boundary_seeking' else 0.0, nf_g.contiguous())
         reward = -(per / nf_g.float())                       # per-sample loss, a constant for the stop head
+        if summary is not None:                              # reward/mean, reward/std (:879-880: before the baseline)
+            reward0 = reward.detach().contiguous()
+            K.vec_stats(reward0, 1.0, out=summary.stat_r)
         rmean = reward.mean().detach()
         if host:
             rmean = float(rmean)
@@ -306,8 +328,15 @@ def g_step_full(g, d, e_g, e_d, opt_g, real, real_len, cs, cl, z0, noise_real, n
         with only_stopper_trains(g, e_g):
             _backward(stopper_surrogate_loss(s, stop_list, reward))
     opt_g.step(clip_norm=ggradclip, check=check)
-    return dict(loss=loss.detach(), bce=bce.detach(), feature_penalty=pen.detach(), z=z, fake=fake.detach(),
-                fake_len=fake_len, s=s.detach(), baseline=baseline, grad_norm=opt_g.last_norm_sum)
+    r = dict(loss=loss.detach(), bce=bce.detach(), feature_penalty=pen.detach(), z=z, fake=fake.detach(),
+             fake_len=fake_len, s=s.detach(), baseline=baseline, grad_norm=opt_g.last_norm_sum)
+    if summary is not None:
+        sr = summary.stat_r
+        summary.commit(1, gen_iter, {2: r['bce'], 3: r['feature_penalty'], 4: r['loss'], 5: sr[0:1], 6: sr[1:2],
+                                     7: baseline.detach() if torch.is_tensor(baseline) else float(baseline),
+                                     8: opt_g.last_norm_sum, 9: float(lambda_fp), 13: opt_g.last_flags})
+        r['reward'] = reward0                                            # (for tests)
+    return r
 
 
 # --------------------------------------------------------------------------------------

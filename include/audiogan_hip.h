@@ -566,6 +566,45 @@ int ag_opt_step(const ag_opt_desc* descs_dev, int n, const float* norms, int kin
                 const int32_t* step_dev, const float* part, float* norms_out, float* norm_sum, int32_t* flags,
                 void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-iteration summaries (audiogan.py:776-809, :875-884, :911-920: the scalars the reference logs) computed on the
+ * device and gathered into a ring the host reads whenever it wants (audiogan_amd/summary.py).  Every reduction sums in
+ * a fixed order (no float atomics): two runs give the same bits.
+ *   ag_logit_summary   one critic output x [B,T] of any (row, column) pitch in elements (sxb, sxt):
+ *                      out5 = { mean, std, hits, mask_sum, hits / mask_sum }; mean / std over ALL B*T entries, population
+ *                      (ddof 0, what numpy's .mean() / .std() give; masked-out positions count), two-pass; hits = the
+ *                      number of entries with t < nframes[b] and x > 0 (positive != 0) or x < 0 (positive == 0),
+ *                      mask_sum = sum_b min(nframes[b], T).  One workgroup; B*T <= 2^22.
+ *   ag_sqnorm_rows     part[b] = scale * sum_l gx[b,l]^2 / nframes[b] for gx [B,L] of row pitch ld (elements), one
+ *                      workgroup per row; out (optional, NULL: the caller sums `part` itself, e.g. ag_summary_commit):
+ *                      out[0] = (sum_b part[b], b ascending) / B, by a finishing launch.
+ *   ag_vec_stats       out2 = { sign * mean(v), population std(v) } of v [n] contiguous, two-pass, one workgroup.
+ *   ag_summary_commit  one row of the ring: column c < 16 = the 32-bit word at src[c] (float or int32 bits, copied as they
+ *                      are) or imm[c] when src[c] is NULL; column 1 = the sequence number cursor[1]; column part_col (if
+ *                      part != NULL) = (sum_b part[b], b ascending) / npart as ag_sqnorm_rows' finishing launch computes
+ *                      it.  The row goes to ring[cursor[0]] (16 words per row); then cursor[0] = (cursor[0] + 1) %
+ *                      capacity and cursor[1] += 1.  `desc_dev` is a DEVICE copy of the descriptor.
+ * ------------------------------------------------------------------------- */
+#define AG_SUMMARY_COLS 16
+typedef struct ag_summary_desc {
+  const void* src[AG_SUMMARY_COLS];
+  uint32_t imm[AG_SUMMARY_COLS];
+  const float* part;
+  uint32_t* ring;    /* [capacity, 16] */
+  int32_t* cursor;   /* [2]: next row, next sequence number */
+  int32_t npart;
+  int32_t part_col;
+  int32_t capacity;
+  int32_t pad_;
+} ag_summary_desc;
+
+int ag_logit_summary(const float* x, int64_t sxb, int64_t sxt, const int64_t* nframes_i64, int positive, float* out5, int B,
+                     int T, void* stream);
+int ag_sqnorm_rows(const float* gx, int64_t ld, const int64_t* nframes_i64, float scale, float* part, float* out, int B, int L,
+                   void* stream);
+int ag_vec_stats(const float* v, float sign, float* out2, int n, void* stream);
+int ag_summary_commit(const ag_summary_desc* desc_dev, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
