@@ -334,7 +334,9 @@ extern "C" int ag_gemm_h(const uint16_t* A, int lda, int ta, const uint16_t* B, 
   p.kchunk = K;
   hipStream_t st = (hipStream_t)stream;
   const int64_t tiles = (int64_t)ag_cdiv(M, 128) * ag_cdiv(N, 128), mn = (int64_t)M * N;
-  if (tiles < 192 && K >= 1024 && act == AG_ACT_NONE && !C16 && !gate16 && ws.p && ws.numel >= 2 * mn) {
+  // (a bf16 residual has no second stage - ag_splitk_reduce adds fp32 ones: such a product runs unsplit and leaves the
+  // workspace that ag_gemm_h_ws_numel asked for unused)
+  if (tiles < 192 && K >= 1024 && act == AG_ACT_NONE && !C16 && !gate16 && !res16 && ws.p && ws.numel >= 2 * mn) {
     int ks = h_pick_ksplit(tiles, mn, K);
     if ((int64_t)ks * mn > ws.numel) ks = (int)(ws.numel / mn);
     if (ks >= 2) {
@@ -351,9 +353,8 @@ extern "C" int ag_gemm_h(const uint16_t* A, int lda, int ta, const uint16_t* B, 
   if (ta == 1 && tb == 1) launch_h<1, 1>(p, grid, st);
   AG_CHECK_LAUNCH("ag_gemm_h");
   if (!p.part) return AG_OK;
-  if (ag_reduces_deferred() && !bias && !res && !res16 && (beta == 0.f || beta == 1.f))
+  if (ag_reduces_deferred() && !bias && !res && (beta == 0.f || beta == 1.f))
     return ag_slab_defer_2d(p.part, p.ksplit, M, N, C, ldc, beta == 1.f ? 1 : 0, st);
-  AG_REQUIRE(!res16, "ag_gemm_h: a split-K product takes its residual in fp32");
   return ag_splitk_reduce(p.part, p.ksplit, mn, M, N, C, ldc, beta, bias, res, ldres, st);
 }
 

@@ -297,7 +297,8 @@ int ag_build_zc(const float* z, const float* c, float* zc, int B, int T, int ns,
  * activation whose derivative scales the result; gate16 (bf16, optional): a saved LeakyReLU output applied AFTER bias /
  * res (a residual layer's backward: (W^T da + da) gated by the layer below).  Shapes: ag_gemm_h_ok (K % 64 == 0, leading
  * dimensions % 8 == 0, row counts % 8 == 0 for k-strided operands, 16-byte aligned operands).  Split-K (fp32 output, plain
- * epilogue) through a bound workspace of ag_gemm_h_ws_numel floats; its second stage is deferrable.
+ * epilogue) through a bound workspace of ag_gemm_h_ws_numel floats; its second stage is deferrable.  A product with a
+ * bf16 residual runs unsplit (the second stage adds fp32 residuals only); a workspace bound for it is left unused.
  * ag_to_bf16_2d: dst[r,c] = bf16(src[r,c]) for a pitched [rows <= 65535, cols] block (weights -> their bf16 image).
  * ------------------------------------------------------------------------- */
 int ag_gemm_h_ok(int M, int N, int K, int ta, int tb, int lda, int ldb);
