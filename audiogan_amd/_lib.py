@@ -35,6 +35,18 @@ class ConvArgs(C.Structure):
                 ('slope', f32), ('accumulate', i32), ('wp_pad', i32)]
 
 
+class FrontFwdArgs(C.Structure):
+    _fields_ = [('struct_bytes', i64), ('cell', i32), ('gen', i32)] + [(n, vp) for n in (
+        'gates', 'gh', 'w_x', 'w_hh', 'b_hn', 'w_p', 'b_p', 'hs', 'cs', 'x', 'xt', 'w_s', 'b_s', 'u', 's', 'first', 't_run',
+        'ws')] + [(n, i64) for n in ('ldx', 'lds', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
+
+
+class FrontBwdArgs(C.Structure):
+    _fields_ = [('struct_bytes', i64), ('cell', i32), ('pad_', i32)] + [(n, vp) for n in (
+        'ga', 'state', 'gh', 'x', 'dh_ext', 'dx_ext', 'w_hh', 'w_x', 'w_p', 'dgs', 'dgh', 'dxt', 'ws')] + [
+        (n, i64) for n in ('ldx', 'lddx', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
+
+
 class OptDesc(C.Structure):
     _fields_ = [('p', vp), ('grad', vp), ('s1', vp), ('s2', vp), ('n', i64)]
 
@@ -114,12 +126,8 @@ SIGNATURES = {
     'ag_gfront_persist_ok': (C.c_int, [C.c_int] * 4),
     'ag_gfront_persist_ws_bytes': (i64, [C.c_int] * 3),
     'ag_gfront_bwd_persist_ok': (C.c_int, [C.c_int] * 4),
-    'ag_gfront_bwd_persist': (C.c_int, [vp, vp, vp, i64, vp, vp, i64, vp, vp, C.c_int, vp, vp, vp, vp, i64] + [C.c_int] * 5 + [vp]),
-    'ag_grufront_bwd_persist': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, C.c_int, vp, vp, vp, vp, vp, i64] + [C.c_int] * 5 + [vp]),
-    'ag_gfront_fwd_persist': (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64] + [C.c_int] * 5 + [vp]),
-    'ag_grufront_fwd_persist': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64] + [C.c_int] * 5 + [vp]),
-    'ag_gfront_gen_persist': (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]
-                              + [C.c_int] * 5 + [vp]),
+    'ag_gfront_fwd': (C.c_int, [C.POINTER(FrontFwdArgs), vp]),
+    'ag_gfront_bwd': (C.c_int, [C.POINTER(FrontBwdArgs), vp]),
     'ag_build_zc': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'ag_critic_batch': (C.c_int, [vp, i64, vp, i64, C.c_int, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp,
                                   C.POINTER(i32), C.c_int, vp, vp, vp, C.c_int, vp, vp]),
@@ -161,7 +169,7 @@ def _load():
     return lib
 
 
-ABI_VERSION = 12      # what this package was written against (csrc/api.hip: ag_abi_version)
+ABI_VERSION = 13      # what this package was written against (csrc/api.hip: ag_abi_version)
 
 lib = _load()
 if lib.ag_abi_version() != ABI_VERSION:

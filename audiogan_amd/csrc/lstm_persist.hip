@@ -71,6 +71,19 @@ static PersistCtl ps_ctl(void* ws) {
   return c;
 }
 
+// The prologue of every persistent host launcher: the workspace check, the memset node that zeroes the header, the control
+// block.  The LAST step before a launcher fills its parameters: ps_ctl consumes the ag_persist_debug arming, and a call that
+// fails validation must not consume it.
+static int persist_begin(const char* who, void* ws, int64_t ws_bytes, int64_t need, hipStream_t st, PersistCtl* ctl) {
+  AG_REQUIRE(ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: workspace too small or misaligned", who);
+  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
+    ag_set_error("%s: memset failed", who);
+    return AG_ERR_LAUNCH;
+  }
+  *ctl = ps_ctl(ws);
+  return AG_OK;
+}
+
 struct PersistDir {
   float* pre;          // [T,B,4H] in: x-projection (+ biases); out: activated gates
   const float* whh;    // [4H,H]
@@ -372,22 +385,16 @@ extern "C" int ag_lstm_seq_fwd_persist(float* const* pre, const float* const* wh
     ag_set_error("ag_lstm_seq_fwd_persist: shape B=%d H=%d ndir=%d does not fit %d CUs", B, H, ndir, n_cu);
     return AG_ERR_UNSUPPORTED;
   }
-  AG_REQUIRE(ws_bytes >= ag_lstm_persist_ws_bytes(B, H, ndir) && ((uintptr_t)ws & 15) == 0,
-             "ag_lstm_seq_fwd_persist: workspace too small or misaligned");
   for (int d = 0; d < ndir; ++d) AG_REQUIRE(((uintptr_t)whh[d] & 15) == 0, "ag_lstm_seq_fwd_persist: W_hh must be 16-B aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_lstm_seq_fwd_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
   PersistFwdP p;
+  if (int rc = persist_begin("ag_lstm_seq_fwd_persist", ws, ws_bytes, ag_lstm_persist_ws_bytes(B, H, ndir), st, &p.ctl)) return rc;
   for (int d = 0; d < 2; ++d) {
     const int s = d < ndir ? d : 0;
     p.d[d].pre = pre[s]; p.d[d].whh = whh[s]; p.d[d].c_all = c_all[s];
     p.d[d].cb = static_pre ? static_pre[s] : nullptr;
   }
   p.y = (float*)y; p.y16 = y_bf16 ? 1 : 0; p.valid = valid_i64;
-  p.ctl = ps_ctl(ws);
   p.xbuf = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
   p.T = T; p.B = B; p.H = H; p.ndir = ndir; p.nbt = nbt; p.ntile = H / 8;
   p.rb = ag_precision() == AG_PREC_BF16;
@@ -636,22 +643,18 @@ extern "C" int ag_lstm_seq_bwd_persist(const float* const* gates, const float* c
     ag_set_error("ag_lstm_seq_bwd_persist: shape B=%d H=%d ndir=%d does not fit %d CUs", B, H, ndir, n_cu);
     return AG_ERR_UNSUPPORTED;
   }
-  AG_REQUIRE(ws_bytes >= PS_STICKY_BYTES + PS_HDR_BYTES && ((uintptr_t)ws & 15) == 0, "ag_lstm_seq_bwd_persist: workspace too small");
   AG_REQUIRE((int64_t)B * 4 * H * 4 < ((int64_t)1 << 31), "ag_lstm_seq_bwd_persist: step slab too large");
+  AG_REQUIRE(!dg16 || dg16_ld >= 4 * H, "ag_lstm_seq_bwd_persist: dg16 row pitch smaller than a row");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_lstm_seq_bwd_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
   PersistBwdP p;
+  if (int rc = persist_begin("ag_lstm_seq_bwd_persist", ws, ws_bytes, PS_STICKY_BYTES + PS_HDR_BYTES, st, &p.ctl)) return rc;
   for (int d = 0; d < 2; ++d) {
     const int s = d < ndir ? d : 0;
     p.d[d].ga = gates[s]; p.d[d].whh = whh[s]; p.d[d].c_all = c_all[s]; p.d[d].dgates = dgates[s];
     p.d[d].dgsum = dgsum ? dgsum[s] : nullptr;
     p.d[d].dg16 = dg16 ? dg16[s] : nullptr;
   }
-  AG_REQUIRE(!dg16 || dg16_ld >= 4 * H, "ag_lstm_seq_bwd_persist: dg16 row pitch smaller than a row");
-  p.dy = (const float*)dy; p.dy16 = dy_bf16 ? 1 : 0; p.dg16_ld = dg16_ld; p.valid = valid_i64; p.ctl = ps_ctl(ws);
+  p.dy = (const float*)dy; p.dy16 = dy_bf16 ? 1 : 0; p.dg16_ld = dg16_ld; p.valid = valid_i64;
   p.T = T; p.B = B; p.H = H; p.ndir = ndir; p.nbt = ag_cdiv(B, 16); p.ntile = H / 32;
   p.rb = ag_precision() == AG_PREC_BF16;
   const int grid = ndir * p.nbt * p.ntile;
@@ -711,7 +714,7 @@ struct FrontFwdP {
   int fs;              // the real frame size: fs % 8 == 0, 8 <= fs <= FS
 };
 
-// Generation mode (GEN = 1, ag_gfront_gen_persist): sampling, no autograd.  No history is written (gates, hs, cs, gh, xt:
+// Generation mode (GEN = 1, ag_gfront_fwd with gen = 1): sampling, no autograd.  No history is written (gates, hs, cs, gh, xt:
 // only x); `gates` holds the pre-activations and is only read.  Per frame the projection workgroups of column tile 0 (ut = 0
 // and 1: one per 16-clip subtile) also form the stop logit s = h_t . w_s + b_s beside their MFMA tile and draw the stop,
 // stop = u[t,b] < sigmoid(s).  Exit rule: every subtile publishes, before its x flag of frame t,
@@ -1190,140 +1193,73 @@ extern "C" int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs) {
   return PS_STICKY_BYTES + PS_HDR_BYTES + (int64_t)2 * ag_cdiv(B, 32) * 32 * (S + w) * 4;
 }
 
-// One launch for the whole frame loop of the Generator front (one LSTMCell layer).  gates [T,B,4S]: in = the z/c
-// part of the pre-activations + both biases, out = activated gates; w_x = W_ih[:, :fs] (row pitch ldwx), w_hh [4S,S],
-// w_p [fs,S], b_p [fs]; outputs hs [T,B,S], cs [T+1,B,S] (cs[0] is written 0 by the launch), x [B,T*fs].  Shapes: ag_gfront_persist_ok.
-extern "C" int ag_gfront_fwd_persist(float* gates, const float* w_x, int ldwx, const float* w_hh, const float* w_p,
-                                     const float* b_p, float* hs, float* cs, float* x, int64_t ldx, float* xt, void* ws,
-                                     int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream) {
-  AG_REQUIRE(gates && w_x && w_hh && w_p && b_p && hs && cs && x && ws, "ag_gfront_fwd_persist: null tensor");
-  AG_REQUIRE(T > 0, "ag_gfront_fwd_persist: T must be positive");
-  AG_REQUIRE(ldx >= (int64_t)T * fs, "ag_gfront_fwd_persist: x row pitch smaller than a row");
-  if (!front_shape_ok(B, S, fs, n_cu)) {
-    ag_set_error("ag_gfront_fwd_persist: shape B=%d S=%d fs=%d is not supported on %d CUs", B, S, fs, n_cu);
-    return AG_ERR_UNSUPPORTED;
-  }
-  AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
-             "ag_gfront_fwd_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
-             "ag_gfront_fwd_persist: weights must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_gfront_fwd_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
-  FrontFwdP p;
-  p.gates = gates; p.gh = nullptr; p.bhn = nullptr; p.wx = w_x; p.whh = w_hh; p.wp = w_p; p.bp = b_p; p.hs = hs; p.cs = cs; p.x = x;
-  p.ldx = ldx; p.xt = xt;
-  p.ctl = ps_ctl(ws);
-  p.nrt = ag_cdiv(B, 32);
-  p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
-  p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
-  const int grid = p.nrt * (S / 8);
-  if (S == 1024) {
-    if (p.rb) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 2>), dim3(grid), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0>), dim3(grid), dim3(512), 0, st, p);
-  } else {
-    hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0>), dim3(grid), dim3(512), 0, st, p);   // (FS/8 per wave is odd)
-  }
-  AG_CHECK_LAUNCH("ag_gfront_fwd_persist");
+// A pointer field of ag_front_fwd_args / ag_front_bwd_args and whether the chosen (cell, gen) uses it: a used field must
+// be set, and a field that is not used must be NULL (a caller that fills a field the launch ignores has mixed up two forms).
+struct FrontField {
+  const char* name;
+  const void* p;
+  bool used;
+};
+
+template <int N>
+static int front_fields_ok(const char* who, const FrontField (&f)[N]) {
+  for (const FrontField& e : f)
+    AG_REQUIRE((e.p != nullptr) == e.used, "%s: %s %s", who, e.name, e.used ? "is NULL" : "is not used by this cell / mode and must be NULL");
   return AG_OK;
 }
 
-// The GRU-front generator's frame loop (BASELINE configs[3]; the feedback loop of audiogan.py:428-460 with a GRU cell, gate
-// order r z n as torch.nn.GRUCell) as ONE persistent launch: the same kernel with the GRU column layout.
-//   gates [T,B,3S]  in: W_ih[:, fs:] zc_t + b_ih + (b_hr, b_hz, 0)  (one GEMM over all frames); out: activated (r, z, n)
-//   gh    [T,B,3S]  out: only the n slot, W_hn h_{t-1} + b_hn (what ag_gru_cell_bwd reads)
-//   w_x = W_ih[:, :fs] (row pitch ldwx), w_hh [3S,S], b_hn [S] = b_hh[2S:], w_p [fs,S], b_p [fs]
-//   hs [T,B,S] (h_t), x [B,T*fs].  Shapes as ag_gfront_persist_ok; workspace as ag_gfront_fwd_persist.
-extern "C" int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x, int ldwx, const float* w_hh,
-                                       const float* b_hn, const float* w_p, const float* b_p, float* hs, float* x, int64_t ldx,
-                                       float* xt, void* ws, int64_t ws_bytes, int T, int B, int S, int fs, int n_cu,
-                                       void* stream) {
-  AG_REQUIRE(gates && gh && w_x && w_hh && b_hn && w_p && b_p && hs && x && ws, "ag_grufront_fwd_persist: null tensor");
-  AG_REQUIRE(T > 0, "ag_grufront_fwd_persist: T must be positive");
-  AG_REQUIRE(ldx >= (int64_t)T * fs, "ag_grufront_fwd_persist: x row pitch smaller than a row");
-  if (!front_shape_ok(B, S, fs, n_cu)) {
-    ag_set_error("ag_grufront_fwd_persist: shape B=%d S=%d fs=%d is not supported on %d CUs", B, S, fs, n_cu);
+// The frame loop of the Generator front in ONE launch: training forward and generation mode, LSTM and GRU cell.  Tensor
+// contracts: ag_front_fwd_args (include/audiogan_hip.h).  Shapes: ag_gfront_persist_ok.
+extern "C" int ag_gfront_fwd(const ag_front_fwd_args* a, void* stream) {
+  static const char* const who = "ag_gfront_fwd";
+  AG_REQUIRE(a && a->struct_bytes == (int64_t)sizeof(*a), "%s: struct_bytes = %lld, but ag_front_fwd_args has %zu bytes in this library",
+             who, a ? (long long)a->struct_bytes : -1LL, sizeof(*a));
+  AG_REQUIRE((a->cell == 0 || a->cell == 1) && (a->gen == 0 || a->gen == 1),
+             "%s: cell must be 0 (LSTM) or 1 (GRU) and gen 0 (training) or 1 (generation)", who);
+  const bool gru = a->cell == 1, gen = a->gen == 1;
+  const FrontField fields[] = {
+      {"gates", a->gates, true}, {"gh", a->gh, gru && !gen}, {"w_x", a->w_x, true}, {"w_hh", a->w_hh, true},
+      {"b_hn", a->b_hn, gru}, {"w_p", a->w_p, true}, {"b_p", a->b_p, true}, {"hs", a->hs, !gen}, {"cs", a->cs, !gru && !gen},
+      {"x", a->x, true}, {"xt", a->xt, !gen && a->xt},      // (optional in training)
+      {"w_s", a->w_s, gen}, {"b_s", a->b_s, gen}, {"u", a->u, gen}, {"s", a->s, gen}, {"first", a->first, gen},
+      {"t_run", a->t_run, gen}, {"ws", a->ws, true}};
+  if (int rc = front_fields_ok(who, fields)) return rc;
+  const int T = a->T, B = a->B, S = a->S, fs = a->fs;
+  AG_REQUIRE(T > 0, "%s: T must be positive", who);
+  AG_REQUIRE(a->ldx >= (int64_t)T * fs, "%s: x row pitch smaller than a row", who);
+  AG_REQUIRE(!gen || a->lds >= T, "%s: s row pitch smaller than a row", who);
+  if (!front_shape_ok(B, S, fs, a->n_cu)) {
+    ag_set_error("%s: shape B=%d S=%d fs=%d is not supported on %d CUs", who, B, S, fs, a->n_cu);
     return AG_ERR_UNSUPPORTED;
   }
-  AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
-             "ag_grufront_fwd_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
-             "ag_grufront_fwd_persist: weights must be 16-byte aligned");
+  AG_REQUIRE(a->ldwx >= fs && a->ldwx % 4 == 0 && (((uintptr_t)a->w_x | (uintptr_t)a->w_hh | (uintptr_t)a->w_p) & 15) == 0,
+             "%s: weights must be 16-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_grufront_fwd_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
-  FrontFwdP p;
-  p.gates = gates; p.gh = gh; p.bhn = b_hn; p.wx = w_x; p.whh = w_hh; p.wp = w_p; p.bp = b_p; p.hs = hs; p.cs = nullptr; p.x = x;
-  p.ldx = ldx; p.xt = xt;
-  p.ctl = ps_ctl(ws);
+  FrontGenP p;      // (the training kernels take its base part, FrontFwdP)
+  if (int rc = persist_begin(who, a->ws, a->ws_bytes, ag_gfront_persist_ws_bytes(B, S, fs), st, &p.ctl)) return rc;
+  p.gates = a->gates; p.gh = a->gh; p.bhn = a->b_hn; p.wx = a->w_x; p.whh = a->w_hh; p.wp = a->w_p; p.bp = a->b_p;
+  p.hs = a->hs; p.cs = a->cs; p.x = a->x; p.ldx = a->ldx; p.xt = a->xt;
+  p.ws = a->w_s; p.bs = a->b_s; p.u = a->u; p.s = a->s; p.lds = a->lds; p.first = a->first; p.t_run = a->t_run;
   p.nrt = ag_cdiv(B, 32);
-  p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
+  p.hx = (float*)((char*)a->ws + PS_STICKY_BYTES + PS_HDR_BYTES);
   p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
+  p.T = T; p.B = B; p.ldwx = a->ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
   const int grid = p.nrt * (S / 8);
-  if (S == 1024) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 1>), dim3(grid), dim3(512), 0, st, p);
-  else hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 1>), dim3(grid), dim3(512), 0, st, p);
-  AG_CHECK_LAUNCH("ag_grufront_fwd_persist");
-  return AG_OK;
-}
-
-// Generation mode of the two fronts above (gfront_persist_fwd_kernel<..., GEN = 1>): the frame loop of a sample, no history.
-//   cell 0 (LSTM): pre [T,B,4S] = the z/c part of the pre-activations + both biases (as ag_gfront_fwd_persist's gates on input)
-//   cell 1 (GRU):  pre [T,B,3S] as ag_grufront_fwd_persist's gates on input; b_hn [S] = b_hh[2S:] (ignored for cell 0)
-//   w_s [S], b_s [1]: the stop head; u [T,B]: uniforms, stop[b,t] = u[t,b] < sigmoid(s[b,t])
-// Outputs: x [B,T*fs] (row pitch ldx) and s [B,T] (row pitch lds) for the frames run; first [B] (int32) = frames clip b
-// generates (1 + its first stop frame, T if it never stops); t_run [1] (int32) = frames run: the launch leaves its loop
-// GEN_LAG frames after every clip has stopped (max(first) + GEN_LAG when that is < T).  `pre` is only read.  Shapes and
-// workspace as ag_gfront_fwd_persist.
-extern "C" int ag_gfront_gen_persist(int cell, const float* pre, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
-                                     const float* w_p, const float* b_p, const float* w_s, const float* b_s, const float* u,
-                                     float* x, int64_t ldx, float* s, int64_t lds, int* first, int* t_run, void* ws,
-                                     int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream) {
-  AG_REQUIRE(cell == 0 || cell == 1, "ag_gfront_gen_persist: cell must be 0 (LSTM) or 1 (GRU)");
-  AG_REQUIRE(pre && w_x && w_hh && w_p && b_p && w_s && b_s && u && x && s && first && t_run && ws && (cell == 0 || b_hn),
-             "ag_gfront_gen_persist: null tensor");
-  AG_REQUIRE(T > 0, "ag_gfront_gen_persist: T must be positive");
-  AG_REQUIRE(ldx >= (int64_t)T * fs, "ag_gfront_gen_persist: x row pitch smaller than a row");
-  AG_REQUIRE(lds >= T, "ag_gfront_gen_persist: s row pitch smaller than a row");
-  if (!front_shape_ok(B, S, fs, n_cu)) {
-    ag_set_error("ag_gfront_gen_persist: shape B=%d S=%d fs=%d is not supported on %d CUs", B, S, fs, n_cu);
-    return AG_ERR_UNSUPPORTED;
-  }
-  AG_REQUIRE(ws_bytes >= ag_gfront_persist_ws_bytes(B, S, fs) && ((uintptr_t)ws & 15) == 0,
-             "ag_gfront_gen_persist: workspace too small or misaligned");
-  AG_REQUIRE(ldwx >= fs && ldwx % 4 == 0 && (((uintptr_t)w_x | (uintptr_t)w_hh | (uintptr_t)w_p) & 15) == 0,
-             "ag_gfront_gen_persist: weights must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_gfront_gen_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
-  FrontGenP p;
-  p.gates = const_cast<float*>(pre);      // (read only in this mode)
-  p.gh = nullptr; p.bhn = cell == 1 ? b_hn : nullptr; p.wx = w_x; p.whh = w_hh; p.wp = w_p; p.bp = b_p;
-  p.hs = nullptr; p.cs = nullptr; p.x = x; p.ldx = ldx; p.xt = nullptr;
-  p.ws = w_s; p.bs = b_s; p.u = u; p.s = s; p.lds = lds; p.first = first; p.t_run = t_run;
-  p.ctl = ps_ctl(ws);
-  p.nrt = ag_cdiv(B, 32);
-  p.hx = (float*)((char*)ws + PS_STICKY_BYTES + PS_HDR_BYTES);
-  p.xx = p.hx + (int64_t)2 * p.nrt * 32 * S;
-  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs; p.rb = ag_precision() == AG_PREC_BF16;
-  const int grid = p.nrt * (S / 8);
-  // (the same kernels as the training forward: the GRU front and S = 128 have no bf16-MFMA form)
-  if (S == 1024) {
-    if (cell == 1) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 1, 1>), dim3(grid), dim3(512), 0, st, p);
-    else if (p.rb) hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 2, 0, 1>), dim3(grid), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gfront_persist_fwd_kernel<1024, 256, 0, 0, 1>), dim3(grid), dim3(512), 0, st, p);
+  // (the GRU front and S = 128 have no bf16-MFMA form)
+  if (!gen) {
+    void (*kern)(const FrontFwdP) =
+        !gru ? (S == 1024 ? (p.rb ? gfront_persist_fwd_kernel<1024, 256, 2> : gfront_persist_fwd_kernel<1024, 256, 0>)
+                          : gfront_persist_fwd_kernel<128, 64, 0>)
+             : (S == 1024 ? gfront_persist_fwd_kernel<1024, 256, 0, 1> : gfront_persist_fwd_kernel<128, 64, 0, 1>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, static_cast<const FrontFwdP&>(p));
   } else {
-    if (cell == 1) hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 1, 1>), dim3(grid), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gfront_persist_fwd_kernel<128, 64, 0, 0, 1>), dim3(grid), dim3(512), 0, st, p);
+    void (*kern)(const FrontGenP);
+    if (S == 1024 && gru) kern = gfront_persist_fwd_kernel<1024, 256, 0, 1, 1>;
+    else if (S == 1024) kern = p.rb ? gfront_persist_fwd_kernel<1024, 256, 2, 0, 1> : gfront_persist_fwd_kernel<1024, 256, 0, 0, 1>;
+    else kern = gru ? gfront_persist_fwd_kernel<128, 64, 0, 1, 1> : gfront_persist_fwd_kernel<128, 64, 0, 0, 1>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, p);
   }
-  AG_CHECK_LAUNCH("ag_gfront_gen_persist");
+  AG_CHECK_LAUNCH(who);
   return AG_OK;
 }
 
@@ -1616,71 +1552,47 @@ static bool front_bwd_shape_ok(int B, int S, int fs, int n_cu) {
 
 extern "C" int ag_gfront_bwd_persist_ok(int B, int S, int fs, int n_cu) { return front_bwd_shape_ok(B, S, fs, n_cu) ? 1 : 0; }
 
-// The frame loop of the Generator front's backward in ONE launch.  ga [T,B,4S] activated gates and c_all [T+1,B,S] as
-// saved by the forward, x [B,T*fs] the front's output (row pitch ldx), the external gradients dh_ext [T,B,S] = dL/dh_t
-// (the stop head's) and dx_ext [B,T*fs] = dL/dx_t (the conv trunk's, row pitch lddx: it may be channel 0 of the trunk's
-// gradient slab) - each read only, each may be NULL = zero -, w_hh [4S,S], w_x = W_ih[:, :fs] (row pitch ldwx), w_p [fs,S]; outputs dgs [T,B,4S] (d gate pre-activations) and
-// dxt [T,B,fs] (d pre-tanh of the projection).  `ws`: >= PS_STICKY_BYTES + 8 KiB (status + flags).
-static int front_bwd_launch(int cell, const float* ga, const float* c_all, const float* gh, const float* x, int64_t ldx,
-                            const float* dh_ext, const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x,
-                            int ldwx, const float* w_p, float* dgs, float* dgh, float* dxt, void* ws, int64_t ws_bytes, int T,
-                            int B, int S, int fs, int n_cu, void* stream);
-
-extern "C" int ag_gfront_bwd_persist(const float* ga, const float* c_all, const float* x, int64_t ldx, const float* dh_ext,
-                                     const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x, int ldwx,
-                                     const float* w_p, float* dgs, float* dxt, void* ws, int64_t ws_bytes, int T, int B,
-                                     int S, int fs, int n_cu, void* stream) {
-  return front_bwd_launch(0, ga, c_all, nullptr, x, ldx, dh_ext, dx_ext, lddx, w_hh, w_x, ldwx, w_p, dgs, dgs, dxt, ws,
-                          ws_bytes, T, B, S, fs, n_cu, stream);
-}
-
-// The same for the GRU front (BASELINE configs[3]; torch.nn.GRUCell, gate order r z n): ga [T,B,3S] activated gates, hs
-// [T+1,B,S] (hs[t] = h_{t-1}, hs[0] = 0) and gh [T,B,3S] (n slot) as saved by ag_grufront_fwd_persist; outputs dgi
-// [T,B,3S] (d of the input-side pre-activations), dgh [T,B,3S] (hidden side: the n slot times r) and dxt [T,B,fs].
-extern "C" int ag_grufront_bwd_persist(const float* ga, const float* hs, const float* gh, const float* x, int64_t ldx,
-                                       const float* dh_ext, const float* dx_ext, int64_t lddx, const float* w_hh,
-                                       const float* w_x, int ldwx, const float* w_p, float* dgi, float* dgh, float* dxt,
-                                       void* ws, int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream) {
-  AG_REQUIRE(gh && dgh, "ag_grufront_bwd_persist: null tensor");
-  return front_bwd_launch(1, ga, hs, gh, x, ldx, dh_ext, dx_ext, lddx, w_hh, w_x, ldwx, w_p, dgi, dgh, dxt, ws, ws_bytes, T,
-                          B, S, fs, n_cu, stream);
-}
-
-static int front_bwd_launch(int cell, const float* ga, const float* c_all, const float* gh, const float* x, int64_t ldx,
-                            const float* dh_ext, const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x,
-                            int ldwx, const float* w_p, float* dgs, float* dgh, float* dxt, void* ws, int64_t ws_bytes, int T,
-                            int B, int S, int fs, int n_cu, void* stream) {
-  AG_REQUIRE(ga && c_all && x && w_hh && w_x && w_p && dgs && dxt && ws, "ag_gfront_bwd_persist: null tensor");
-  AG_REQUIRE(T > 0, "ag_gfront_bwd_persist: T must be positive");
-  AG_REQUIRE(ldx >= (int64_t)T * fs && (!dx_ext || lddx >= (int64_t)T * fs), "ag_gfront_bwd_persist: row pitch smaller than a row");
-  if (!front_bwd_shape_ok(B, S, fs, n_cu)) {
-    ag_set_error("ag_gfront_bwd_persist: shape B=%d S=%d fs=%d is not supported on %d CUs", B, S, fs, n_cu);
+// The frame loop of the front's backward through time in ONE launch, LSTM and GRU cell.  Tensor contracts:
+// ag_front_bwd_args (include/audiogan_hip.h).  Shapes: ag_gfront_bwd_persist_ok.
+extern "C" int ag_gfront_bwd(const ag_front_bwd_args* a, void* stream) {
+  static const char* const who = "ag_gfront_bwd";
+  AG_REQUIRE(a && a->struct_bytes == (int64_t)sizeof(*a), "%s: struct_bytes = %lld, but ag_front_bwd_args has %zu bytes in this library",
+             who, a ? (long long)a->struct_bytes : -1LL, sizeof(*a));
+  AG_REQUIRE(a->cell == 0 || a->cell == 1, "%s: cell must be 0 (LSTM) or 1 (GRU)", who);
+  const bool gru = a->cell == 1;
+  const FrontField fields[] = {
+      {"ga", a->ga, true}, {"state", a->state, true}, {"gh", a->gh, gru}, {"x", a->x, true},
+      {"dh_ext", a->dh_ext, a->dh_ext != nullptr}, {"dx_ext", a->dx_ext, a->dx_ext != nullptr},      // (optional)
+      {"w_hh", a->w_hh, true}, {"w_x", a->w_x, true}, {"w_p", a->w_p, true}, {"dgs", a->dgs, true}, {"dgh", a->dgh, gru},
+      {"dxt", a->dxt, true}, {"ws", a->ws, true}};
+  if (int rc = front_fields_ok(who, fields)) return rc;
+  const int T = a->T, B = a->B, S = a->S, fs = a->fs;
+  AG_REQUIRE(T > 0, "%s: T must be positive", who);
+  AG_REQUIRE(a->ldx >= (int64_t)T * fs && (!a->dx_ext || a->lddx >= (int64_t)T * fs), "%s: row pitch smaller than a row", who);
+  if (!front_bwd_shape_ok(B, S, fs, a->n_cu)) {
+    ag_set_error("%s: shape B=%d S=%d fs=%d is not supported on %d CUs", who, B, S, fs, a->n_cu);
     return AG_ERR_UNSUPPORTED;
   }
-  AG_REQUIRE(ws_bytes >= PS_STICKY_BYTES + PS_HDR_BYTES && ((uintptr_t)ws & 15) == 0, "ag_gfront_bwd_persist: workspace too small");
-  AG_REQUIRE(ldwx >= fs, "ag_gfront_bwd_persist: bad row pitch");
-  AG_REQUIRE((int64_t)B * 4 * S * 4 < ((int64_t)1 << 31), "ag_gfront_bwd_persist: frame slab too large");
-  AG_REQUIRE((((uintptr_t)dgs | (uintptr_t)dxt) & 15) == 0, "ag_gfront_bwd_persist: outputs must be 16-byte aligned");
+  AG_REQUIRE(a->ldwx >= fs, "%s: bad row pitch", who);
+  AG_REQUIRE((int64_t)B * 4 * S * 4 < ((int64_t)1 << 31), "%s: frame slab too large", who);
+  AG_REQUIRE((((uintptr_t)a->dgs | (uintptr_t)a->dxt) & 15) == 0, "%s: outputs must be 16-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + PS_STICKY_BYTES, 0, PS_HDR_BYTES, st) != hipSuccess) {
-    ag_set_error("ag_gfront_bwd_persist: memset failed");
-    return AG_ERR_LAUNCH;
-  }
   FrontBwdP p;
-  p.ga = ga; p.c_all = c_all; p.x = x; p.ldx = ldx; p.dh_ext = dh_ext; p.dx_ext = dx_ext; p.lddx = lddx; p.w_hh = w_hh; p.w_x = w_x; p.w_p = w_p; p.dgs = dgs; p.dxt = dxt;
-  p.gh = gh; p.dgh = dgh;
-  p.ctl = ps_ctl(ws);
-  p.T = T; p.B = B; p.ldwx = ldwx; p.fs = fs;
+  if (int rc = persist_begin(who, a->ws, a->ws_bytes, PS_STICKY_BYTES + PS_HDR_BYTES, st, &p.ctl)) return rc;
+  p.ga = a->ga; p.c_all = a->state; p.x = a->x; p.ldx = a->ldx; p.dh_ext = a->dh_ext; p.dx_ext = a->dx_ext; p.lddx = a->lddx;
+  p.w_hh = a->w_hh; p.w_x = a->w_x; p.w_p = a->w_p; p.dgs = a->dgs; p.dxt = a->dxt;
+  p.gh = a->gh; p.dgh = gru ? a->dgh : a->dgs;      // (LSTM: the field is not read)
+  p.T = T; p.B = B; p.ldwx = a->ldwx; p.fs = fs;
   const bool rb = ag_precision() == AG_PREC_BF16;
   const int grid = front_bwd_grid(B, S, fs);
   void (*kern)(const FrontBwdP);
-  if (cell == 0)
+  if (!gru)
     kern = S == 1024 ? (rb ? gfront_persist_bwd_kernel<1024, 256, true, 0> : gfront_persist_bwd_kernel<1024, 256, false, 0>)
                      : (rb ? gfront_persist_bwd_kernel<128, 64, true, 0> : gfront_persist_bwd_kernel<128, 64, false, 0>);
   else
     kern = S == 1024 ? (rb ? gfront_persist_bwd_kernel<1024, 256, true, 1> : gfront_persist_bwd_kernel<1024, 256, false, 1>)
                      : (rb ? gfront_persist_bwd_kernel<128, 64, true, 1> : gfront_persist_bwd_kernel<128, 64, false, 1>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, p);
-  AG_CHECK_LAUNCH("ag_gfront_bwd_persist");
+  AG_CHECK_LAUNCH(who);
   return AG_OK;
 }

@@ -1167,24 +1167,42 @@ def _rows(t, name, B, n):
     return t.stride(0) if B > 1 else max(t.stride(0), n)
 
 
+_PITCHED = 'pitched'      # mark in a _front_check table: a 2-D view of unit stride along dim 1 and any row pitch
+
+
+def _front_check(table):
+    """the tensor checks of the fronts' persistent launches.  Rows (tensor, name, shape[, dtype or _PITCHED]): a device tensor
+    of that dtype (fp32 by default) and shape, dense unless marked _PITCHED (channel 0 of a slab, a column block of a
+    weight).  A tensor that is None (an optional one) is skipped.  Returns {name: row pitch} of the _PITCHED rows (0: None)"""
+    ld = {}
+    for t, name, shp, *kind in table:
+        if kind == [_PITCHED]:
+            ld[name] = _rows(t, name, *shp) if t is not None else 0
+        elif t is not None:
+            _chk(t, name, *kind)
+            assert t.is_contiguous() and tuple(t.shape) == shp, (name, tuple(t.shape), shp)
+    return ld
+
+
+def _front_launch(entry, args, dev, ws_bytes):
+    """fills in what every launch of the fronts sets the same way (struct size, workspace, CUs) and calls lib.<entry>"""
+    ws = _persist_workspace(dev, ws_bytes)
+    args.struct_bytes, args.ws, args.ws_bytes, args.n_cu = C.sizeof(args), ws.data_ptr(), ws.numel(), _n_cu(dev)
+    check(getattr(lib, entry)(C.byref(args), _stream()), entry)
+
+
 def gfront_fwd_persist(gates, wx, whh, wp, bp, hs, cs, x, xt=None):
-    """the Generator front's frame loop in ONE persistent launch (ag_gfront_fwd_persist).  x: [B, T*fs] rows of any pitch
-    (channel 0 of the conv trunk's slab); xt: optional [T,B,fs], receives the same frames time-major"""
+    """the Generator front's frame loop in ONE persistent launch (ag_gfront_fwd, LSTM cell, training).  x: [B, T*fs] rows of
+    any pitch (channel 0 of the conv trunk's slab); xt: optional [T,B,fs], receives the same frames time-major"""
     T, B, S4 = gates.shape
     S = S4 // 4
     fs = wp.size(0)
-    for t_, n, shp in ((gates, 'gates', (T, B, 4 * S)), (whh, 'whh', (4 * S, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
-                       (hs, 'hs', (T, B, S)), (cs, 'cs', (T + 1, B, S))) + (((xt, 'xt', (T, B, fs)),) if xt is not None else ()):
-        _chk(t_, n)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    ldx = _rows(x, 'x', B, T * fs)
-    _chk(wx, 'wx')
-    assert tuple(wx.shape) == (4 * S, fs) and wx.stride(1) == 1
-    nb = int(lib.ag_gfront_persist_ws_bytes(B, S, fs))
-    ws = _persist_workspace(x.device, nb)
-    check(lib.ag_gfront_fwd_persist(_p(gates), _p(wx), wx.stride(0), _p(whh), _p(wp), _p(bp), _p(hs), _p(cs), _p(x), ldx,
-                                    _p(xt), _p(ws), ws.numel(), T, B, S, fs, _n_cu(x.device), _stream()),
-          'ag_gfront_fwd_persist')
+    ld = _front_check(((gates, 'gates', (T, B, 4 * S)), (whh, 'whh', (4 * S, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
+                       (hs, 'hs', (T, B, S)), (cs, 'cs', (T + 1, B, S)), (xt, 'xt', (T, B, fs)),
+                       (x, 'x', (B, T * fs), _PITCHED), (wx, 'wx', (4 * S, fs), _PITCHED)))
+    a = _lib.FrontFwdArgs(cell=0, gen=0, gates=_p(gates), w_x=_p(wx), ldwx=ld['wx'], w_hh=_p(whh), w_p=_p(wp), b_p=_p(bp),
+                          hs=_p(hs), cs=_p(cs), x=_p(x), ldx=ld['x'], xt=_p(xt), T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_fwd', a, x.device, int(lib.ag_gfront_persist_ws_bytes(B, S, fs)))
 
 
 # the front's backward runs beside the conv trunk's gradient all-reduce in the multi-GPU step (train.GraphedStep, phase
@@ -1212,51 +1230,37 @@ def gfront_bwd_persist_ok(B, S, fs, dev):
                 and lib.ag_gfront_bwd_persist_ok(B, S, fs, _n_cu(dev)))
 
 
-def _ext_grads(dh_ext, dx_ext, T, B, S, fs):
-    if dh_ext is not None:
-        _chk(dh_ext, 'dh_ext')
-        assert dh_ext.is_contiguous() and tuple(dh_ext.shape) == (T, B, S), tuple(dh_ext.shape)
-    return _rows(dx_ext, 'dx_ext', B, T * fs) if dx_ext is not None else 0
-
-
 def gfront_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, wx, wp, dgs, dxt):
-    """the backward through time of the Generator front's frame loop in ONE persistent launch (ag_gfront_bwd_persist);
+    """the backward through time of the Generator front's frame loop in ONE persistent launch (ag_gfront_bwd, LSTM cell);
     the external gradients, read only, each may be None: dh_ext [T,B,S] = dL/dh_t (the stop head's), dx_ext [B,T*fs] rows of
     any pitch = dL/dx_t (the conv trunk's: channel 0 of its gradient slab); x likewise [B,T*fs] rows of any pitch"""
     T, B, S4 = gates.shape
     S = S4 // 4
     fs = wp.size(0)
-    for t_, n, shp in ((gates, 'gates', (T, B, 4 * S)), (cs, 'cs', (T + 1, B, S)), (whh, 'whh', (4 * S, S)),
-                       (wp, 'wp', (fs, S)), (dgs, 'dgs', (T, B, 4 * S)), (dxt, 'dxt', (T, B, fs))):
-        _chk(t_, n)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    ldx, lddx = _rows(x, 'x', B, T * fs), _ext_grads(dh_ext, dx_ext, T, B, S, fs)
-    _chk(wx, 'wx')
-    assert tuple(wx.shape) == (4 * S, fs) and wx.stride(1) == 1
-    ws = _persist_workspace(x.device, _PERSIST_WS_MIN)
-    check(lib.ag_gfront_bwd_persist(_p(gates), _p(cs), _p(x), ldx, _p(dh_ext), _p(dx_ext), lddx, _p(whh), _p(wx),
-                                    wx.stride(0), _p(wp), _p(dgs), _p(dxt), _p(ws), ws.numel(), T, B, S, fs,
-                                    _n_cu(x.device), _stream()), 'ag_gfront_bwd_persist')
+    ld = _front_check(((gates, 'gates', (T, B, 4 * S)), (cs, 'cs', (T + 1, B, S)), (whh, 'whh', (4 * S, S)),
+                       (wp, 'wp', (fs, S)), (dgs, 'dgs', (T, B, 4 * S)), (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)),
+                       (x, 'x', (B, T * fs), _PITCHED), (dx_ext, 'dx_ext', (B, T * fs), _PITCHED),
+                       (wx, 'wx', (4 * S, fs), _PITCHED)))
+    a = _lib.FrontBwdArgs(cell=0, ga=_p(gates), state=_p(cs), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext), dx_ext=_p(dx_ext),
+                          lddx=ld['dx_ext'], w_hh=_p(whh), w_x=_p(wx), ldwx=ld['wx'], w_p=_p(wp), dgs=_p(dgs), dxt=_p(dxt),
+                          T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_bwd', a, x.device, _PERSIST_WS_MIN)
 
 
 def grufront_bwd_persist(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, dgi, dgh, dxt):
-    """the GRU front's backward through time in ONE persistent launch (ag_grufront_bwd_persist); hs [T+1,B,S] with
+    """the GRU front's backward through time in ONE persistent launch (ag_gfront_bwd, GRU cell); hs [T+1,B,S] with
     hs[t] = h_{t-1}; dh_ext / dx_ext: the external gradients as for gfront_bwd_persist"""
     T, B, S3 = gates.shape
     S = S3 // 3
     fs = wp.size(0)
-    for t_, n, shp in ((gates, 'gates', (T, B, 3 * S)), (hs, 'hs', (T + 1, B, S)), (gh, 'gh', (T, B, 3 * S)),
-                       (whh, 'whh', (3 * S, S)), (wp, 'wp', (fs, S)),
-                       (dgi, 'dgi', (T, B, 3 * S)), (dgh, 'dgh', (T, B, 3 * S)), (dxt, 'dxt', (T, B, fs))):
-        _chk(t_, n)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    ldx, lddx = _rows(x, 'x', B, T * fs), _ext_grads(dh_ext, dx_ext, T, B, S, fs)
-    _chk(wx, 'wx')
-    assert tuple(wx.shape) == (3 * S, fs) and wx.stride(1) == 1
-    ws = _persist_workspace(x.device, _PERSIST_WS_MIN)
-    check(lib.ag_grufront_bwd_persist(_p(gates), _p(hs), _p(gh), _p(x), ldx, _p(dh_ext), _p(dx_ext), lddx, _p(whh), _p(wx),
-                                      wx.stride(0), _p(wp), _p(dgi), _p(dgh), _p(dxt), _p(ws), ws.numel(), T, B, S, fs,
-                                      _n_cu(x.device), _stream()), 'ag_grufront_bwd_persist')
+    ld = _front_check(((gates, 'gates', (T, B, 3 * S)), (hs, 'hs', (T + 1, B, S)), (gh, 'gh', (T, B, 3 * S)),
+                       (whh, 'whh', (3 * S, S)), (wp, 'wp', (fs, S)), (dgi, 'dgi', (T, B, 3 * S)), (dgh, 'dgh', (T, B, 3 * S)),
+                       (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)), (x, 'x', (B, T * fs), _PITCHED),
+                       (dx_ext, 'dx_ext', (B, T * fs), _PITCHED), (wx, 'wx', (3 * S, fs), _PITCHED)))
+    a = _lib.FrontBwdArgs(cell=1, ga=_p(gates), state=_p(hs), gh=_p(gh), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext),
+                          dx_ext=_p(dx_ext), lddx=ld['dx_ext'], w_hh=_p(whh), w_x=_p(wx), ldwx=ld['wx'], w_p=_p(wp),
+                          dgs=_p(dgi), dgh=_p(dgh), dxt=_p(dxt), T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_bwd', a, x.device, _PERSIST_WS_MIN)
 
 
 def _work_grufront_bwd(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, *a_, **kw):
@@ -1267,27 +1271,21 @@ def _work_grufront_bwd(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, *a_, **kw)
 
 
 def grufront_fwd_persist(gates, gh, wx, whh, bhn, wp, bp, hs, x, xt=None):
-    """the GRU-front generator's frame loop in ONE persistent launch (ag_grufront_fwd_persist); hs: [T,B,S] (h_t); x / xt as
-    for gfront_fwd_persist"""
+    """the GRU-front generator's frame loop in ONE persistent launch (ag_gfront_fwd, GRU cell, training); hs: [T,B,S] (h_t);
+    x / xt as for gfront_fwd_persist"""
     T, B, S3 = gates.shape
     S = S3 // 3
     fs = wp.size(0)
-    for t_, n, shp in ((gates, 'gates', (T, B, 3 * S)), (gh, 'gh', (T, B, 3 * S)), (whh, 'whh', (3 * S, S)), (bhn, 'bhn', (S,)),
-                       (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)), (hs, 'hs', (T, B, S))) + (((xt, 'xt', (T, B, fs)),) if xt is not None else ()):
-        _chk(t_, n)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    ldx = _rows(x, 'x', B, T * fs)
-    _chk(wx, 'wx')
-    assert tuple(wx.shape) == (3 * S, fs) and wx.stride(1) == 1
-    nb = int(lib.ag_gfront_persist_ws_bytes(B, S, fs))
-    ws = _persist_workspace(x.device, nb)
-    check(lib.ag_grufront_fwd_persist(_p(gates), _p(gh), _p(wx), wx.stride(0), _p(whh), _p(bhn), _p(wp), _p(bp), _p(hs),
-                                      _p(x), ldx, _p(xt), _p(ws), ws.numel(), T, B, S, fs, _n_cu(x.device), _stream()),
-          'ag_grufront_fwd_persist')
+    ld = _front_check(((gates, 'gates', (T, B, 3 * S)), (gh, 'gh', (T, B, 3 * S)), (whh, 'whh', (3 * S, S)), (bhn, 'bhn', (S,)),
+                       (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)), (hs, 'hs', (T, B, S)), (xt, 'xt', (T, B, fs)),
+                       (x, 'x', (B, T * fs), _PITCHED), (wx, 'wx', (3 * S, fs), _PITCHED)))
+    a = _lib.FrontFwdArgs(cell=1, gen=0, gates=_p(gates), gh=_p(gh), w_x=_p(wx), ldwx=ld['wx'], w_hh=_p(whh), b_hn=_p(bhn),
+                          w_p=_p(wp), b_p=_p(bp), hs=_p(hs), x=_p(x), ldx=ld['x'], xt=_p(xt), T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_fwd', a, x.device, int(lib.ag_gfront_persist_ws_bytes(B, S, fs)))
 
 
 def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=None):
-    """the generation mode of the fronts' persistent launch (ag_gfront_gen_persist): the frame loop of a sample, no history.
+    """the generation mode of the fronts' persistent launch (ag_gfront_fwd, gen = 1): the frame loop of a sample, no history.
     pre [T,B,4S] (LSTM front) or [T,B,3S] (GRU front, then ``bhn`` [S] = b_hh[2S:]) is only read; ws = the stop head's
     weight (S elements), bs [1]; u [T,B] uniforms.  Writes x [B, T*fs] (rows of any pitch: channel 0 of the conv trunk's
     slab), s [B,T] (rows of any pitch >= T), first [B] int32 (frames per clip) and t_run [1] int32 (frames run), all for
@@ -1297,23 +1295,16 @@ def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=
     fs = wp.size(0)
     cell = 1 if SG == 3 * S else 0
     assert SG == (3 if cell else 4) * S, (tuple(pre.shape), tuple(whh.shape))
-    for t_, n, shp in ((pre, 'pre', (T, B, SG)), (whh, 'whh', (SG, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
-                       (bs, 'bs', (1,)), (u, 'u', (T, B))) + (((bhn, 'bhn', (S,)),) if cell else ()):
-        _chk(t_, n)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    _chk(ws, 'ws')
-    assert ws.is_contiguous() and ws.numel() == S, tuple(ws.shape)
-    ldx, lds = _rows(x, 'x', B, T * fs), _rows(s, 's', B, T)
-    for t_, n, shp in ((first, 'first', (B,)), (t_run, 't_run', (1,))):
-        _chk(t_, n, torch.int32)
-        assert t_.is_contiguous() and tuple(t_.shape) == shp, (n, tuple(t_.shape), shp)
-    _chk(wx, 'wx')
-    assert tuple(wx.shape) == (SG, fs) and wx.stride(1) == 1
-    nb = int(lib.ag_gfront_persist_ws_bytes(B, S, fs))
-    wsp = _persist_workspace(x.device, nb)
-    check(lib.ag_gfront_gen_persist(cell, _p(pre), _p(wx), wx.stride(0), _p(whh), _p(bhn if cell else None), _p(wp), _p(bp),
-                                    _p(ws), _p(bs), _p(u), _p(x), ldx, _p(s), lds, _p(first), _p(t_run), _p(wsp), wsp.numel(),
-                                    T, B, S, fs, _n_cu(x.device), _stream()), 'ag_gfront_gen_persist')
+    assert ws.numel() == S, tuple(ws.shape)
+    bhn = bhn if cell else None
+    ld = _front_check(((pre, 'pre', (T, B, SG)), (whh, 'whh', (SG, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
+                       (bs, 'bs', (1,)), (u, 'u', (T, B)), (bhn, 'bhn', (S,)), (ws, 'ws', tuple(ws.shape)),
+                       (first, 'first', (B,), torch.int32), (t_run, 't_run', (1,), torch.int32),
+                       (x, 'x', (B, T * fs), _PITCHED), (s, 's', (B, T), _PITCHED), (wx, 'wx', (SG, fs), _PITCHED)))
+    a = _lib.FrontFwdArgs(cell=cell, gen=1, gates=_p(pre), w_x=_p(wx), ldwx=ld['wx'], w_hh=_p(whh), b_hn=_p(bhn), w_p=_p(wp),
+                          b_p=_p(bp), w_s=_p(ws), b_s=_p(bs), u=_p(u), x=_p(x), ldx=ld['x'], s=_p(s), lds=ld['s'],
+                          first=_p(first), t_run=_p(t_run), T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_fwd', a, x.device, int(lib.ag_gfront_persist_ws_bytes(B, S, fs)))
 
 
 def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):

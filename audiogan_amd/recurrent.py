@@ -358,6 +358,22 @@ def _frames_buffer(front, B, n, dev):
     return torch.empty(B, n, device=dev)
 
 
+def _front_pre(zc, wz, b_ih, b_hh, pre, gru):
+    """the part of the fronts' gate pre-activations that does not wait for the frame loop, all frames in one GEMM, in the form
+    the persistent launches take: pre [T,B,G*S] = zc_t @ W_ih[:, fs:]^T + b_ih + b_hh.  LSTM: the second bias as a `res` of row
+    pitch 0 (no launch to add the two vectors first).  GRU: only the r / z halves of b_hh ride along, b_hn stays apart (it
+    sits inside r * (...))"""
+    T, B, Fz = zc.shape
+    zc2, pre2 = zc.contiguous().view(T * B, Fz), pre.view(T * B, pre.size(2))
+    if gru:
+        S = b_hh.numel() // 3
+        bias = b_ih.clone()
+        bias[:2 * S] += b_hh[:2 * S]
+        K.gemm(zc2, wz, pre2, tb=True, bias=bias)
+    else:
+        K.gemm(zc2, wz, pre2, tb=True, bias=b_ih, res=_bcast_rows(b_hh, T * B))
+
+
 class GFront(object):
     """WN items: per layer [w_ih, w_hh, b_ih, b_hh] * num_layers, then [proj.w, proj.b, stop.w, stop.b]"""
 
@@ -387,10 +403,7 @@ class GFrontFn(torch.autograd.Function):
         cs = [torch.empty(T + 1, B, S, device=dev) for _ in range(nl)]
         w_ih0 = lw[0][0]
         wx, wz = w_ih0[:, :fs], w_ih0[:, fs:]
-        # all frames at once: zc_t @ W_ih[:, fs:]^T + b_ih + b_hh (the second bias as a `res` of row pitch 0: no launch to
-        # add the two vectors first)
-        K.gemm(zc.contiguous().view(T * B, Fz), wz, gates[0].view(T * B, 4 * S), tb=True, bias=lw[0][2],
-               res=_bcast_rows(lw[0][3], T * B))
+        _front_pre(zc, wz, lw[0][2], lw[0][3], gates[0], gru=False)
         fused0 = K.lstm_step_ok(B, S, x[:, :fs], wx)
         persist = nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev)
         xt = None
@@ -467,7 +480,7 @@ class GFrontFn(torch.autograd.Function):
 
     @staticmethod
     def _bwd_frames_fused(T, B, fs, S, x, dx, ds, gates, cs, w_hh, wx, pw, sw, hs, dws, nl):
-        """single-layer front: ONE persistent launch where the shape fits (ag_gfront_bwd_persist), else TWO launches per
+        """single-layer front: ONE persistent launch where the shape fits (ag_gfront_bwd), else TWO launches per
         frame: dacc[t] = [dL/dh_t | dL/dx_t] lives in one [B, S+fs] row so that  dacc[t-1] += dgates_t @ [W_hh |
         W_ih[:, :fs]]  is ONE product, and the tanh backward of the projection, its product and the cell backward are one
         fused step (ag_lstm_front_bwd_step)."""
@@ -482,7 +495,7 @@ class GFrontFn(torch.autograd.Function):
         dgs = torch.empty(T, B, 4 * S, device=dev)
         dxt = torch.empty(T, B, fs, device=dev)
         if persist:
-            # the whole loop in ONE launch, [W_hh | W_x] and W_p resident in registers (ag_gfront_bwd_persist).  The external
+            # the whole loop in ONE launch, [W_hh | W_x] and W_p resident in registers (ag_gfront_bwd).  The external
             # gradients are read where they are: dL/dx_t from the trunk's gradient (any row pitch: channel 0 of its slab),
             # dL/dh_t (the stop head's, if any) from a [T,B,S] product - no [T,B,S+fs] staging tensor to fill and copy into
             dh_ext = None
@@ -612,11 +625,8 @@ class GRUFrontFn(torch.autograd.Function):
         hs[0].zero_()
         persist = T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev)
         if persist:
-            # the whole frame loop (GRU step + projection, fed back) in ONE launch, weights resident in registers: the r / z
-            # halves of b_hh ride with the precomputed input part, b_hn stays apart (it sits inside r * (...))
-            bias = b_ih.clone()
-            bias[:2 * S] += b_hh[:2 * S]
-            K.gemm(zc.contiguous().view(T * B, Fz), wz, gi.view(T * B, 3 * S), tb=True, bias=bias)
+            # the whole frame loop (GRU step + projection, fed back) in ONE launch, weights resident in registers
+            _front_pre(zc, wz, b_ih, b_hh, gi, gru=True)
             xt = torch.empty(T, B, fs, device=dev)
             K.grufront_fwd_persist(gi, gh, wx, w_hh, b_hh[2 * S:].contiguous(), pw, pb, hs[1:], x, xt)
         else:
@@ -665,7 +675,7 @@ class GRUFrontFn(torch.autograd.Function):
                 dh_ext = torch.empty(T, B, S, device=dev)
             K.gemm(ds_tb, sw, dh_ext.view(T * B, S) if persist else dha[1:].view(T * B, S))
         if persist:
-            # the whole loop in ONE launch (ag_grufront_bwd_persist); the external gradients dL/dh_t, dL/dx_t are read in place
+            # the whole loop in ONE launch (ag_gfront_bwd); the external gradients dL/dh_t, dL/dx_t are read in place
             dx_ext = dx if (dx is None or dx.stride(1) == 1) else dx.contiguous()
             K.grufront_bwd_persist(gi, hs, gh, x, dh_ext, dx_ext, w_hh, wx, pw, dgi, dgh, dxt)
         dh_dir = None if persist else torch.empty(B, S, device=dev)
@@ -712,7 +722,7 @@ def front_sample(front, zc, u):
     t when u[t,b] < sigmoid(s[b,t]) (the reference's Bernoulli draw, :450).  Returns (x [B, T*fs], s [B,T], first int64 [B])
     where first[b] = the frames clip b generates; only the first max(first) frames of x and s are meaningful.
 
-    Where the persistent launch fits (one layer, a supported (B, S, fs)): ONE ag_gfront_gen_persist launch, which draws the
+    Where the persistent launch fits (one layer, a supported (B, S, fs)): ONE ag_gfront_fwd launch (gen = 1), which draws the
     stops itself, keeps no history and leaves its frame loop one frame after every clip has stopped.  Otherwise the training
     front runs over all T frames under no_grad and the same rule is applied to its logits."""
     T, B, Fz = zc.shape
@@ -725,15 +735,8 @@ def front_sample(front, zc, u):
     pw, pb, sw, sb = [p_.w for p_ in prep[4 * nl:4 * nl + 4]]
     wx, wz = w_ih[:, :fs], w_ih[:, fs:]
     if nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev):
-        zc2 = zc.contiguous().view(T * B, Fz)
-        if gru:
-            pre = torch.empty(T, B, 3 * S, device=dev)
-            bias = b_ih.clone()
-            bias[:2 * S] += b_hh[:2 * S]
-            K.gemm(zc2, wz, pre.view(T * B, 3 * S), tb=True, bias=bias)
-        else:
-            pre = torch.empty(T, B, 4 * S, device=dev)
-            K.gemm(zc2, wz, pre.view(T * B, 4 * S), tb=True, bias=b_ih, res=_bcast_rows(b_hh, T * B))
+        pre = torch.empty(T, B, (3 if gru else 4) * S, device=dev)
+        _front_pre(zc, wz, b_ih, b_hh, pre, gru)
         x = _frames_buffer(front, B, T * fs, dev)
         s = torch.empty(B, T, device=dev)
         first = torch.empty(B, dtype=torch.int32, device=dev)

@@ -403,72 +403,88 @@ int ag_lstm_seq_bwd_persist(const float* const* gates, const float* const* whh, 
                             int dg16_ld /* row pitch of dg16 in elements, >= 4H */, const int64_t* valid_i64, void* ws,
                             int64_t ws_bytes, int T, int B, int H, int ndir, int n_cu, void* stream);
 
-/* The Generator front's whole frame loop (audiogan.py:428-460, one LSTMCell layer + tanh(proj) fed back) as ONE
- * persistent launch with every weight resident in registers (csrc/lstm_persist.hip).  gates [T,B,4S]: in = the z / c
- * part of the gate pre-activations + both biases (one GEMM over all frames), out = activated gates; w_x = W_ih[:, :fs]
- * (row pitch ldwx), w_hh [4S,S], w_p [fs,S], b_p [fs]; outputs hs [T,B,S], cs [T+1,B,S] (cs[0] is written 0 by the launch) and the
- * frames x [B,T*fs].  Supported (ag_gfront_persist_ok): S = 1024 with any frame size fs % 8 == 0, 8 <= fs <= 256 (the
- * reference's default 200 among them), S = 128 with fs % 8 == 0, 8 <= fs <= 64; B <= 64 and ceil(B/32) * S/8 <= n_cu.  The
- * kernels keep the x panel at the padded width 256 / 64: lanes at or past fs hold zeros, rows of x have the pitch fs.  `ws` =
- * ag_gfront_persist_ws_bytes() bytes (sized for the padded width: the same for every fs of a state size), used as for
- * ag_lstm_seq_fwd_persist. */
+/* The Generator front's whole frame loop (audiogan.py:428-460: one recurrent cell + tanh(proj) fed back) as ONE
+ * persistent launch with every weight resident in registers (csrc/lstm_persist.hip), in two modes:
+ *   training (gen 0): `gates` comes in as the z / c part of the pre-activations (one GEMM over all frames) and goes out
+ *     activated; the history the backward needs (hs, cs or gh, xt) is written beside the frames x.
+ *   generation (gen 1, Generator.generate): the frame loop of a SAMPLE, trains nothing and keeps no history - `gates` is only
+ *     read and only x is written.  Per frame the launch also forms the stop logit s[b,t] = h_t[b] . w_s + b_s and draws
+ *     stop[b,t] = u[t,b] < sigmoid(s[b,t]) from the caller's uniforms (audiogan.py:444-460: a Bernoulli(p) draw, stated as a
+ *     function of u so that it can be reproduced).  The loop ends early, by one rule every workgroup takes from the same
+ *     write-once words: before frame t + 1 it reads the decisions of frame t - 1 (a lag of one frame) and leaves iff every
+ *     clip has stopped by then, so t_run = min(T, max(first) + 1).  Frames past max(first) are correct frames the caller
+ *     discards; x and s are written for the frames run only.
+ * and with two cells: 0 = LSTMCell (G = 4 gate blocks i f g o), 1 = GRU cell (BASELINE configs[3]: the LSTMCell of :380-386
+ * replaced by a GRU cell; G = 3, gate order r z n as torch.nn.GRUCell).
+ * Supported (ag_gfront_persist_ok): S = 1024 with any frame size fs % 8 == 0, 8 <= fs <= 256 (the reference's default 200
+ * among them), S = 128 with fs % 8 == 0, 8 <= fs <= 64; B <= 64 and ceil(B/32) * S/8 <= n_cu.  The kernels keep the x panel
+ * at the padded width 256 / 64: lanes at or past fs hold zeros, rows of x have the pitch fs (in generation mode the stop
+ * workgroups are those of column tile 0, which every fs has).  `ws` = ag_gfront_persist_ws_bytes() bytes (sized for the
+ * padded width: the same for every fs of a state size), used as for ag_lstm_seq_fwd_persist.
+ *
+ * Every tensor is fp32 and dense in the stated shape unless a pitch (in elements) is named; w_x, w_hh, w_p and `ws` are
+ * 16-byte aligned, ldwx % 4 == 0.  A field that the chosen (cell, gen) does not use must be NULL. */
+typedef struct ag_front_fwd_args {
+  int64_t struct_bytes; /* sizeof(ag_front_fwd_args): a caller built against another layout is refused */
+  int32_t cell;         /* 0 LSTM, 1 GRU */
+  int32_t gen;          /* 0 training, 1 generation */
+  float* gates;         /* all: [T,B,G*S].  in: W_ih[:, fs:] zc_t + b_ih + (LSTM: b_hh; GRU: (b_hr, b_hz, 0));
+                           training: out = activated gates; generation: only read */
+  float* gh;            /* GRU training: [T,B,3S] out, only its n slot is written (W_hn h_{t-1} + b_hn, what the backward reads) */
+  const float* w_x;     /* all: W_ih[:, :fs], [G*S,fs] with row pitch ldwx */
+  const float* w_hh;    /* all: [G*S,S] */
+  const float* b_hn;    /* GRU, both modes: [S] = b_hh[2S:] */
+  const float* w_p;     /* all: [fs,S] */
+  const float* b_p;     /* all: [fs] */
+  float* hs;            /* training: [T,B,S] out, h_t */
+  float* cs;            /* LSTM training: [T+1,B,S] out (cs[0] is written 0 by the launch) */
+  float* x;             /* all: [B,T*fs] out, row pitch ldx: the caller may hand over channel 0 of the conv trunk's
+                           activation slab, so the frames land where the trunk reads them (no copy) */
+  float* xt;            /* training, optional: [T,B,fs] out, the same frames time-major (what the weight-gradient products read) */
+  const float* w_s;     /* generation: [S], the materialised stop head */
+  const float* b_s;     /* generation: [1] */
+  const float* u;       /* generation: [T,B] uniforms */
+  float* s;             /* generation: [B,T] out, row pitch lds >= T: the stop logits */
+  int32_t* first;       /* generation: [B] out, the frames clip b generates (1 + its first stop frame, T if it never stops) */
+  int32_t* t_run;       /* generation: [1] out, the frames run */
+  void* ws;             /* all: the workspace */
+  int64_t ldx, lds, ws_bytes;
+  int32_t ldwx, T, B, S, fs, n_cu;
+} ag_front_fwd_args;
 int ag_gfront_persist_ok(int B, int S, int fs, int n_cu);
 int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs);
-/* (round 4) x [B,T*fs] has a row pitch `ldx`: the caller may hand over channel 0 of the conv trunk's activation slab, so the
- * frames land where the trunk reads them (no copy); `xt` (optional) receives the same frames time-major [T,B,fs], the layout
- * the weight-gradient products over all frames read. */
-int ag_gfront_fwd_persist(float* gates, const float* w_x, int ldwx, const float* w_hh, const float* w_p,
-                          const float* b_p, float* hs, float* cs, float* x, int64_t ldx, float* xt, void* ws,
-                          int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream);
+int ag_gfront_fwd(const ag_front_fwd_args* a, void* stream);
 
-/* The frame loop of the Generator front's BACKWARD through time (audiogan.py:437-443 under .backward() :903) in one
- * persistent launch: per frame gx_t = (dx_ext[t] + dgates_{t+1} W_x)(1 - x_t^2), dh_t = dh_ext[t] + dgates_{t+1} W_hh +
- * gx_t W_p, dgates_t = cell backward.  ga [T,B,4S] activated gates and c_all [T+1,B,S] as saved by ag_gfront_fwd_persist,
- * x [B,T*fs] (row pitch ldx); the external gradients dh_ext [T,B,S] = dL/dh_t (the stop head's) and dx_ext [B,T*fs] =
- * dL/dx_t (the conv trunk's; row pitch lddx - it may be channel 0 of the trunk's gradient slab), each read only and each
- * NULL = zero; w_hh [4S,S], w_x = W_ih[:, :fs] (row pitch ldwx), w_p [fs,S]; outputs dgs [T,B,4S] and dxt [T,B,fs] (d pre-tanh of the projection), which the weight-gradient
- * GEMMs over all frames read.  Supported (ag_gfront_bwd_persist_ok): (S, fs) as for ag_gfront_persist_ok and a grid of
- * ceil(B/32) * (S/16 + ceil(fs/16)) workgroups <= n_cu (154 at B = 64, S = 1024, fs = 200);
- * `ws`: the sticky word + 8 KiB header (see ag_lstm_seq_fwd_persist). */
+/* The frame loop of the front's BACKWARD through time (audiogan.py:437-443 under .backward() :903) in one persistent
+ * launch: per frame gx_t = (dx_ext[t] + dgates_{t+1} W_x)(1 - x_t^2), dh_t = dh_ext[t] + dgates_{t+1} W_hh + gx_t W_p,
+ * dgates_t = cell backward (cell 1: torch.nn.GRUCell's).  Reads what the training forward saved; the outputs are what the
+ * weight-gradient GEMMs over all frames read.  Supported (ag_gfront_bwd_persist_ok): (S, fs) as for ag_gfront_persist_ok
+ * and a grid of ceil(B/32) * (S/16 + ceil(fs/16)) workgroups <= n_cu (154 at B = 64, S = 1024, fs = 200); `ws`: the sticky
+ * word + 8 KiB header (see ag_lstm_seq_fwd_persist).  Tensors fp32 and dense as above (G = 4 / 3); dgs, dxt and `ws` are
+ * 16-byte aligned; a field the cell does not use must be NULL. */
+typedef struct ag_front_bwd_args {
+  int64_t struct_bytes; /* sizeof(ag_front_bwd_args) */
+  int32_t cell;         /* 0 LSTM, 1 GRU */
+  int32_t pad_;
+  const float* ga;      /* both: [T,B,G*S] activated gates */
+  const float* state;   /* LSTM: c_all [T+1,B,S]; GRU: hs [T+1,B,S] (hs[t] = h_{t-1}, hs[0] = 0) */
+  const float* gh;      /* GRU: [T,B,3S], n slot = W_hn h_{t-1} + b_hn */
+  const float* x;       /* both: [B,T*fs] the front's output, row pitch ldx */
+  const float* dh_ext;  /* both, optional (NULL = zero): [T,B,S] = dL/dh_t, the stop head's; read only */
+  const float* dx_ext;  /* both, optional (NULL = zero): [B,T*fs] = dL/dx_t, the conv trunk's, row pitch lddx (it may be
+                           channel 0 of the trunk's gradient slab); read only */
+  const float* w_hh;    /* both: [G*S,S] */
+  const float* w_x;     /* both: W_ih[:, :fs], row pitch ldwx */
+  const float* w_p;     /* both: [fs,S] */
+  float* dgs;           /* both: [T,B,G*S] out.  LSTM: d gate pre-activations; GRU: dgi, d of the input-side pre-activations */
+  float* dgh;           /* GRU: [T,B,3S] out, hidden side (the n slot times r) */
+  float* dxt;           /* both: [T,B,fs] out, d pre-tanh of the projection */
+  void* ws;
+  int64_t ldx, lddx, ws_bytes;
+  int32_t ldwx, T, B, S, fs, n_cu;
+} ag_front_bwd_args;
 int ag_gfront_bwd_persist_ok(int B, int S, int fs, int n_cu);
-int ag_gfront_bwd_persist(const float* ga, const float* c_all, const float* x, int64_t ldx, const float* dh_ext,
-                          const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x, int ldwx,
-                          const float* w_p, float* dgs, float* dxt, void* ws, int64_t ws_bytes, int T, int B, int S, int fs,
-                          int n_cu, void* stream);
-/* The same for the GRU-front generator (BASELINE configs[3]; torch.nn.GRUCell backward, gate order r z n): ga [T,B,3S]
- * activated gates, hs [T+1,B,S] (hs[t] = h_{t-1}, hs[0] = 0) and gh [T,B,3S] (n slot = W_hn h_{t-1} + b_hn) as saved by
- * ag_grufront_fwd_persist; outputs dgi [T,B,3S] (d of the input-side pre-activations), dgh [T,B,3S] (hidden side: the n slot
- * times r) and dxt [T,B,fs].  Shapes (any fs % 8 == 0 up to the panel width of S) and workspace as ag_gfront_bwd_persist. */
-int ag_grufront_bwd_persist(const float* ga, const float* hs, const float* gh, const float* x, int64_t ldx,
-                            const float* dh_ext, const float* dx_ext, int64_t lddx, const float* w_hh, const float* w_x,
-                            int ldwx, const float* w_p, float* dgi, float* dgh, float* dxt, void* ws, int64_t ws_bytes, int T,
-                            int B, int S, int fs, int n_cu, void* stream);
-
-/* The same frame loop with a GRU cell (BASELINE configs[3]: the audiogan.py Generator with the LSTMCell of :380-386 replaced
- * by a GRU cell, gate order r z n as torch.nn.GRUCell) as ONE persistent launch.  gates [T,B,3S]: in = W_ih[:, fs:] zc_t +
- * b_ih + (b_hr, b_hz, 0), out = activated (r, z, n); gh [T,B,3S]: only its n slot is written (W_hn h_{t-1} + b_hn, what
- * ag_gru_cell_bwd reads); w_x = W_ih[:, :fs] (row pitch ldwx), w_hh [3S,S], b_hn [S] = b_hh[2S:], w_p [fs,S], b_p [fs];
- * outputs hs [T,B,S] and the frames x [B,T*fs].  Shapes (any fs % 8 == 0 up to the panel width of S) and workspace as for ag_gfront_fwd_persist. */
-int ag_grufront_fwd_persist(float* gates, float* gh, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
-                            const float* w_p, const float* b_p, float* hs, float* x, int64_t ldx, float* xt, void* ws,
-                            int64_t ws_bytes, int T, int B, int S, int fs, int n_cu, void* stream);
-
-/* (v11) Generation mode of the two fronts above: the frame loop of a SAMPLE (Generator.generate), trains nothing and keeps no
- * history - gates, hidden / cell states and time-major frames are not written.  cell 0 (LSTM): pre [T,B,4S] as
- * ag_gfront_fwd_persist's gates on input; cell 1 (GRU): pre [T,B,3S] as ag_grufront_fwd_persist's gates on input, b_hn [S]
- * (ignored, may be NULL, for cell 0); pre is only read.  Per frame the launch also forms the stop logit s[b,t] = h_t[b] . w_s +
- * b_s (w_s [S], b_s [1]: the materialised stop head) and draws stop[b,t] = u[t,b] < sigmoid(s[b,t]) from the caller's
- * uniforms u [T,B] (audiogan.py:444-460: a Bernoulli(p) draw, stated as a function of u so that it can be reproduced).
- * Outputs: the frames x [B,T*fs] (row pitch ldx) and s [B,T] (row pitch lds >= T) of the frames run; first [B] (int32) = the
- * frames clip b generates (1 + its first stop frame, T if it never stops); t_run [1] (int32) = the frames run.  The loop ends
- * early, by one rule every workgroup takes from the same write-once words: before frame t + 1 it reads the decisions of
- * frame t - 1 (a lag of one frame) and leaves iff every clip has stopped by then, so t_run = min(T, max(first) + 1).  Frames
- * past max(first) are correct frames the caller discards.  Shapes (any fs % 8 == 0 up to the panel width of S: the stop
- * workgroups are those of column tile 0, which every fs has) and workspace as for ag_gfront_fwd_persist. */
-int ag_gfront_gen_persist(int cell, const float* pre, const float* w_x, int ldwx, const float* w_hh, const float* b_hn,
-                          const float* w_p, const float* b_p, const float* w_s, const float* b_s, const float* u, float* x,
-                          int64_t ldx, float* s, int64_t lds, int* first, int* t_run, void* ws, int64_t ws_bytes, int T, int B,
-                          int S, int fs, int n_cu, void* stream);
+int ag_gfront_bwd(const ag_front_bwd_args* a, void* stream);
 
 /* One fused backward step of the Generator front (audiogan.py:428-460: LSTMCell -> tanh(Linear) fed back), frame t:
  *   gx     = dxa * (1 - x_t^2)                        d(pre-tanh) of the projection, stored to gx_out [B,Kp]

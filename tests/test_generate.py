@@ -1,6 +1,6 @@
 """Generator.generate (sampling with the stop draws and the early exit of the frame loop), the TrainLoop sampling hook and
 audio.write_wav - host logic on CPU, the HIP kernels replaced by the torch model of tests/kernel_model.py.  The generation
-launch itself (ag_gfront_gen_persist) is modelled here (``gfront_gen_persist``): the persistent host path runs on it when
+launch itself (ag_gfront_fwd, gen = 1) is modelled here (``gfront_gen_persist``): the persistent host path runs on it when
 ``gfront_persist_ok`` is patched to True.  The real launch is covered by tests/test_gpu_generate.py (-m gpu)."""
 import os
 import struct
@@ -16,7 +16,7 @@ GEN_LAG = 1      # lstm_persist.hip: the exit test before frame t + 1 reads the 
 
 
 def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=None):
-    """torch model of ag_gfront_gen_persist (include/audiogan_hip.h): the frame loop with the stop draws and the exit rule"""
+    """torch model of ag_gfront_fwd in generation mode (include/audiogan_hip.h): the frame loop with the stop draws and the exit rule"""
     T, B, SG = pre.shape
     S, fs = whh.size(1), wp.size(0)
     gru = SG == 3 * S

@@ -1,4 +1,4 @@
-"""-m gpu: the generation mode of the fronts' persistent launch (ag_gfront_gen_persist) and Generator.generate on the HIP
+"""-m gpu: the generation mode of the fronts' persistent launch (ag_gfront_fwd, gen = 1) and Generator.generate on the HIP
 kernels - against the training front, against Generator.forward given the same stop draws, on the per-frame fallback, in
 bf16 mode and between the replays of a graphed TrainLoop."""
 import numpy as np

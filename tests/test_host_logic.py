@@ -346,12 +346,12 @@ def test_gru_generator_reports_its_persistent_front(monkeypatch):
     assert g.front_is_persistent(4, torch.device('cpu')) is False
 
 
-def test_abi_12_and_last_kernel_is_empty_on_a_fresh_thread():
+def test_abi_13_and_last_kernel_is_empty_on_a_fresh_thread():
     """ag_last_kernel is per thread (the profiler reads it on the thread that made the call): a thread that has made no
     naming call sees the empty string"""
     import threading
     from audiogan_amd._lib import lib, ABI_VERSION
-    assert ABI_VERSION == 12 and lib.ag_abi_version() == 12
+    assert ABI_VERSION == 13 and lib.ag_abi_version() == 13
     seen = []
     t = threading.Thread(target=lambda: seen.append(lib.ag_last_kernel()))
     t.start()

@@ -1,5 +1,5 @@
 """Generator.generate at the C2 widths (B = 64, S = 1024, fs = 256, T = 32) on HIP events: the frames the sampling loop ran
-(t_run) and the time of the front alone (the z/c pre-activation GEMM + the ag_gfront_gen_persist launch), for three kinds of
+(t_run) and the time of the front alone (the z/c pre-activation GEMM + the ag_gfront_fwd launch (gen = 1)), for three kinds of
 stop uniforms u:
 
     never    u = 1: no clip stops, all 32 frames run
