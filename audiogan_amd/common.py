@@ -119,26 +119,29 @@ class network_backward(object):
 
 
 class Bf16Images(object):
-    """bfloat16 images of fp32 tensors (weights, or column blocks of them), made by ONE small launch each and cached until
-    the source changes: what ag_gemm_h reads on the bf16-storage path.  The key follows WNGroup's: parameter pointer /
-    version / epoch, and the capture tag - inside a hipGraph capture the first use re-converts, so a replayed graph never
-    reads an image that was filled outside it."""
+    """``stack``: one bfloat16 tensor whose row blocks are images of fp32 weights (or column blocks of them), each made by ONE
+    small launch and kept until its Parameter changes: what ag_gemm_h reads on the bf16-storage path.  The key follows
+    WNGroup's: parameter pointer / version / epoch, and the capture tag - inside a hipGraph capture the first use
+    re-converts, so a replayed graph never reads an image that was filled outside it.
 
-    def __init__(self):
-        self._img = {}
+    The holder is kept as an ATTRIBUTE of the Parameter it serves (as ``_ag_epoch`` is), so it can be neither outlived nor
+    mistaken for another tensor's, whatever ids and addresses get reused.  ``state_dict`` (what checkpoint.save writes)
+    carries no attributes; a pickle of the Parameter itself stores None in its place."""
 
-    def get(self, name, src, owner=None):
-        """``src``: a 2-D fp32 tensor (any row pitch) or contiguous; ``owner``: the Parameter whose version identifies its
-        content (default: src itself)"""
-        o = owner if owner is not None else src
-        key = (capture_tag(src.device), o.data_ptr(), o._version, param_epoch(o), src.data_ptr(), tuple(src.shape))
-        hit = self._img.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        buf = hit[1] if (hit is not None and hit[1].shape == src.shape and hit[1].device == src.device) else None
-        img = K.to_bf16(src, out=buf)
-        self._img[name] = (key, img)
-        return img
+    def __init__(self, rows, cols, dev):
+        self.stack = torch.empty(rows, cols, device=dev, dtype=torch.bfloat16)
+        self.keys = {}
+
+    def __reduce__(self):
+        return (type(None), ())
+
+    def fill(self, r0, p, cols):
+        """rows [r0, r0 + p.size(0)) of the stack = p[:, :cols], converted only when ``p`` (a Parameter: its version and
+        epoch identify its content) changed since the last call"""
+        key = (capture_tag(p.device), p.data_ptr(), p._version, param_epoch(p))
+        if self.keys.get(r0) != key:
+            K.to_bf16(p.data[:, :cols], out=self.stack[r0:r0 + p.size(0)])
+            self.keys[r0] = key
 
 
 class Prepared(object):

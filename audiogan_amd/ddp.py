@@ -6,6 +6,8 @@ distributed path, only per-submodule ``NN.DataParallel``."""
 import torch
 import torch.distributed as dist
 
+from .common import bump_param_epoch
+
 
 class GradBucket(object):
     """Owns the flat gradient buffer of one network."""
@@ -89,3 +91,4 @@ def broadcast_parameters(module, src=0, group=None):
     for p in ps:
         p.copy_(flat[o:o + p.numel()].view(p.shape))
         o += p.numel()
+    bump_param_epoch(module.parameters())      # (a write through .data moves no version: say so to WNGroup / Bf16Images)

@@ -298,96 +298,46 @@ def _gh(A, B, C=None, C16=None, ta=False, tb=False, bias=None, res=None, gate=No
         C16.copy_(out)
 
 
+def _prod(A, B, out, **k):
+    """out = A @ B with K.gemm's transpose / epilogue arguments, on the operands as they are stored: fp32 operands take
+    K.gemm, bfloat16 ones ag_gemm_h (_gh), where the output's own dtype says which of its two outputs is meant"""
+    if A.dtype == torch.bfloat16:
+        _gh(A, B, **{'C16' if out.dtype == torch.bfloat16 else 'C': out}, **k)
+    else:
+        K.gemm(A, B, out, **k)
+
+
 class DHeadFn(torch.autograd.Function):
-    """``rows`` fp32: the round-3 form.  ``rows`` bfloat16 (bf16 storage): every activation of the heads, its gradient and
-    both operands of every product are bfloat16 in HBM (ag_gemm_h); logits, parameter gradients and biases stay fp32."""
+    """``rows`` fp32: every activation fp32.  ``rows`` bfloat16 (bf16 storage): every activation of the heads, its gradient
+    and both operands of every product are bfloat16 in HBM (ag_gemm_h); logits, parameter gradients and biases stay fp32.
+    Storage decides the dtype of the activations (they follow ``rows``), the weight operand (``_weights``) and with them
+    the kernel (_prod), and how the residual skip goes backward (``backward``); the rest is common."""
 
     @staticmethod
-    def _forward16(ctx, rows, head, prep):
-        g = head.group
-        M, nr = rows.size(0), head.n_res
-        a = rows.contiguous()
-        saved = [a]
-        for i in range(nr):
-            y = torch.empty(M, prep[2 * i].w.size(0), device=a.device, dtype=torch.bfloat16)
-            _gh(a, g.w16(2 * i), C16=y, tb=True, bias=prep[2 * i + 1].w, res=a, act=ACT_LEAKY)
-            saved.append(y)
-            a = y
-        w1, b0, b1 = prep[2 * nr + 2].w, prep[2 * nr + 1].w, prep[2 * nr + 3].w
-        hmid = torch.empty(M, prep[2 * nr].w.size(0), device=a.device, dtype=torch.bfloat16)
-        _gh(a, g.w16(2 * nr), C16=hmid, tb=True, bias=b0, act=ACT_LEAKY)
-        out = torch.empty(M, w1.size(0), device=a.device)
-        if w1.size(0) == 1 and K.rowdot_ok(hmid, w1):
-            K.rowdot_fwd(hmid, w1, b1, out)
-        else:
-            _gh(hmid, g.w16(2 * nr + 2), C=out, tb=True, bias=b1)
-        saved.append(hmid)
-        ctx.head, ctx.key, ctx.store16 = head, g._key[1:], True
-        ctx.save_for_backward(*saved)
-        return out
-
-    @staticmethod
-    def _backward16(ctx, dout, head, prep):
-        g = head.group
-        saved = ctx.saved_tensors
-        hmid, acts, nr = saved[-1], saved[:-1], head.n_res
-        wg = any(ctx.needs_input_grad[2:])
-        dws = g.zero_dws() if wg else None
-        dout = dout.contiguous()
-        with K.deferred_reduces():
-            w1 = prep[2 * nr + 2].w
-            dh = torch.empty_like(hmid)
-            dw1, db1 = (dws[2 * nr + 2], dws[2 * nr + 3]) if wg else (None, None)
-            if w1.size(0) == 1 and K.rowdot_ok(hmid, w1) and (not wg or db1.data_ptr() == dw1.data_ptr() + 4 * dw1.numel()):
-                K.rowdot_bwd(dout, hmid, w1, dx=dh, dw=dw1, db=db1, gate=True)
-            else:
-                d16 = dout.to(torch.bfloat16)
-                if wg:
-                    _gh(d16, hmid, C=dws[2 * nr + 2], ta=True, defer=True)
-                    K.col_sum(dout, dws[2 * nr + 3])
-                _gh(d16, g.w16(2 * nr + 2), C16=dh, res=hmid, act=ACT_LEAKY_GATE)
-            if wg:
-                _gh(dh, acts[nr], C=dws[2 * nr], ta=True, defer=True)
-                K.col_sum(dh, dws[2 * nr + 1])
-            da = torch.empty_like(acts[nr])
-            if nr > 0:
-                _gh(dh, g.w16(2 * nr), C16=da, res=acts[nr], act=ACT_LEAKY_GATE)
-            else:
-                _gh(dh, g.w16(2 * nr), C16=da)
-            for i in reversed(range(nr)):
-                if wg:
-                    _gh(da, acts[i], C=dws[2 * i], ta=True, defer=True)
-                    K.col_sum(da, dws[2 * i + 1])
-                dprev = torch.empty_like(acts[i])
-                # d(input of residual i) = W^T da + da, times the LeakyReLU derivative of the residual below (gate)
-                _gh(da, g.w16(2 * i), C16=dprev, res=da, gate=acts[i] if i > 0 else None)
-                da = dprev
-        grads = g.backward(dws) if wg else [None] * (2 * len(g.items))
-        return (da if ctx.needs_input_grad[0] else None, None) + tuple(grads)
+    def _weights(head, prep, rows):
+        """i -> the weight operand of item i: the fp32 materialisation, or its bf16 image on bf16 storage"""
+        return head.group.w16 if rows.dtype == torch.bfloat16 else (lambda i: prep[i].w)
 
     @staticmethod
     def forward(ctx, rows, head, *params):
         prep = head.group.prepare()
-        if rows.dtype == torch.bfloat16:
-            return DHeadFn._forward16(ctx, rows, head, prep)
-        ctx.store16 = False
-        M = rows.size(0)
+        W = DHeadFn._weights(head, prep, rows)
+        M, nr = rows.size(0), head.n_res
         a = rows.contiguous()
         saved = [a]
-        for i in range(head.n_res):
-            w, b = prep[2 * i].w, prep[2 * i + 1].w
-            y = torch.empty(M, w.size(0), device=a.device)
-            K.gemm(a, w, y, tb=True, bias=b, res=a, act=ACT_LEAKY)
+        for i in range(nr):
+            y = torch.empty(M, prep[2 * i].w.size(0), device=a.device, dtype=a.dtype)
+            _prod(a, W(2 * i), y, tb=True, bias=prep[2 * i + 1].w, res=a, act=ACT_LEAKY)
             saved.append(y)
             a = y
-        w0, b0, w1, b1 = [p.w for p in prep[2 * head.n_res:2 * head.n_res + 4]]
-        hmid = torch.empty(M, w0.size(0), device=a.device)
-        K.gemm(a, w0, hmid, tb=True, bias=b0, act=ACT_LEAKY)
+        w1, b0, b1 = prep[2 * nr + 2].w, prep[2 * nr + 1].w, prep[2 * nr + 3].w
+        hmid = torch.empty(M, prep[2 * nr].w.size(0), device=a.device, dtype=a.dtype)
+        _prod(a, W(2 * nr), hmid, tb=True, bias=b0, act=ACT_LEAKY)
         out = torch.empty(M, w1.size(0), device=a.device)
         if w1.size(0) == 1 and K.rowdot_ok(hmid, w1):
             K.rowdot_fwd(hmid, w1, b1, out)          # a Linear with one output: one wave per row, no padded MFMA tile
         else:
-            K.gemm(hmid, w1, out, tb=True, bias=b1)
+            _prod(hmid, W(2 * nr + 2), out, tb=True, bias=b1)
         saved.append(hmid)
         ctx.head, ctx.key = head, head.group._key[1:]
         ctx.save_for_backward(*saved)
@@ -398,17 +348,24 @@ class DHeadFn(torch.autograd.Function):
         head = ctx.head
         prep = head.group.prepare()
         assert head.group._key[1:] == ctx.key, 'parameters changed between forward and backward'
-        if ctx.store16:
-            return DHeadFn._backward16(ctx, dout, head, prep)
         saved = ctx.saved_tensors
         hmid = saved[-1]
         acts = saved[:-1]          # acts[0] = input rows, acts[i] = output of residual i
+        s16 = acts[0].dtype == torch.bfloat16
+        W = DHeadFn._weights(head, prep, acts[0])
         nr = head.n_res
         wg = any(ctx.needs_input_grad[2:])
         dws = head.group.zero_dws() if wg else None
         dout = dout.contiguous()
+        # d(input of residual i) = W^T da + da (skip connection), times the LeakyReLU derivative of the residual below:
+        #   'fold'  fp32 precision: (W + I)^T da - with the identity folded into the weight the skip needs no second epilogue
+        #           tensor and `res` is free for the gate of the residual below;
+        #   'add'   bf16 precision on fp32 storage: rounding 1 + w_ii to bfloat16 would lose the diagonal weights, so the skip
+        #           stays an exact fp32 add in the epilogue and the gate a pass of its own;
+        #   'gate'  bf16 storage: ag_gemm_h's epilogue takes both, res = da and gate = the saved activation.
+        skip = 'gate' if s16 else ('fold' if K.get_precision() != 'bf16' else 'add')
         with K.deferred_reduces():      # the bias sums' second stages in ONE launch (nothing below reads them)
-            w0, w1 = prep[2 * nr].w, prep[2 * nr + 2].w
+            w1 = prep[2 * nr + 2].w
             dh = torch.empty_like(hmid)
             dw1, db1 = (dws[2 * nr + 2], dws[2 * nr + 3]) if wg else (None, None)
             if w1.size(0) == 1 and K.rowdot_ok(hmid, w1) and (not wg or db1.data_ptr() == dw1.data_ptr() + 4 * dw1.numel()):
@@ -418,33 +375,31 @@ class DHeadFn(torch.autograd.Function):
                 K.rowdot_bwd(dout, hmid, w1, dx=dh, dw=dw1, db=db1, gate=True)
             else:
                 # classifier[2]: out = hmid @ w1^T + b1
+                d = dout.to(torch.bfloat16) if s16 else dout
                 if wg:
-                    K.gemm(dout, hmid, dws[2 * nr + 2], ta=True, defer=True)
-                    K.col_sum(dout, dws[2 * nr + 3])
+                    _prod(d, hmid, dw1, ta=True, defer=True)
+                    K.col_sum(dout, db1)
                 # every LeakyReLU backward rides in the epilogue of the product that feeds it (ACT_LEAKY_GATE: res = the
                 # saved activation), so dh / da below are d(pre-activation) as they leave the GEMM
-                K.gemm(dout, w1, dh, res=hmid, act=ACT_LEAKY_GATE)
+                _prod(d, W(2 * nr + 2), dh, res=hmid, act=ACT_LEAKY_GATE)
             # classifier[0]
             if wg:
-                K.gemm(dh, acts[nr], dws[2 * nr], ta=True, defer=True)
+                _prod(dh, acts[nr], dws[2 * nr], ta=True, defer=True)
                 K.col_sum(dh, dws[2 * nr + 1])
             da = torch.empty_like(acts[nr])
             if nr > 0:
-                K.gemm(dh, w0, da, res=acts[nr], act=ACT_LEAKY_GATE)
+                _prod(dh, W(2 * nr), da, res=acts[nr], act=ACT_LEAKY_GATE)
             else:
-                K.gemm(dh, w0, da)
-            fold = K.get_precision() != 'bf16'
+                _prod(dh, W(2 * nr), da)
             for i in reversed(range(nr)):
                 if wg:
-                    K.gemm(da, acts[i], dws[2 * i], ta=True, defer=True)
+                    _prod(da, acts[i], dws[2 * i], ta=True, defer=True)
                     K.col_sum(da, dws[2 * i + 1])
                 dprev = torch.empty_like(acts[i])
-                # d(input of residual i) = W^T da + da (skip connection) = (W + I)^T da: with the identity folded into the
-                # weight the skip needs no second epilogue tensor and `res` is free for the gate of the residual below
-                # (not in bf16 mode: rounding 1 + w_ii to bfloat16 would lose the diagonal weights; there the skip stays an
-                # exact fp32 add in the epilogue and the gate a pass of its own)
-                wi = prep[2 * i].w
-                if i > 0 and fold:
+                wi = W(2 * i)
+                if skip == 'gate':
+                    _prod(da, wi, dprev, res=da, gate=acts[i] if i > 0 else None)
+                elif skip == 'fold' and i > 0:
                     K.gemm(da, wi + _eye(wi), dprev, res=acts[i], act=ACT_LEAKY_GATE)
                 else:
                     K.gemm(da, wi, dprev, res=da)

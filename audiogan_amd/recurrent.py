@@ -11,11 +11,13 @@ by ONE C call; other shapes take the generic GEMM + pointwise path.  Everything 
 depend on the recurrence (input projections, weight gradients, stopper head) is batched over
 all time steps into a few large GEMMs.
 """
+import contextlib
+
 import torch
 
 from . import kernels as K
 from .kernels import ACT_NONE, ACT_TANH
-from .common import WNGroup, _zeros_like_list, grad_target
+from .common import Bf16Images, WNGroup, _zeros_like_list, grad_target
 
 
 # set inside losses.only_stopper_trains: the backward that runs there is the REINFORCE update of the stop head, whose
@@ -23,8 +25,8 @@ from .common import WNGroup, _zeros_like_list, grad_target
 STOPPER_ONLY = [False]
 
 
-def _gh(*a, **k):
-    from .ops import _gh as f
+def _prod(*a, **k):
+    from .ops import _prod as f
     return f(*a, **k)
 
 
@@ -61,37 +63,18 @@ def _small_acc(A, B, Cm, tb=False):
 # --------------------------------------------------------------------------------------
 # LSTM layer over a padded sequence (uni- or bidirectional), NN.LSTM parameter layout
 # --------------------------------------------------------------------------------------
-_LSTM_IMAGES = {}      # id(first weight Parameter of a layer) -> common.Bf16Images (bf16 images of that layer's weights)
-
-
-def _lstm_images(w):
-    from .common import Bf16Images
-    key = id(w[0])
-    im = _LSTM_IMAGES.get(key)
-    if im is None:
-        if len(_LSTM_IMAGES) > 64:
-            _LSTM_IMAGES.clear()
-        im = _LSTM_IMAGES[key] = Bf16Images()
-    return im
-
-
 def _wih16(w, ndir, Fx):
     """[ndir * 4H, Fx] bfloat16: the x-columns of every direction's W_ih stacked - the B operand of the input projections
-    (per direction: a row block, k contiguous) and of the input gradient dx = [dg_0 | dg_1] @ stack (k strided)"""
-    im = _lstm_images(w)
+    (per direction: a row block, k contiguous) and of the input gradient dx = [dg_0 | dg_1] @ stack (k strided).  ``w``: the
+    layer's PARAMETERS (forward and backward alike - a saved ``.data`` alias has neither their version nor their epoch); the
+    images belong to the first of them (common.Bf16Images)"""
     H4 = w[0].size(0)
-    stack = getattr(im, 'stack', None)
-    if stack is None or stack.shape != (ndir * H4, Fx) or stack.device != w[0].device:
-        stack = im.stack = torch.empty(ndir * H4, Fx, device=w[0].device, dtype=torch.bfloat16)
-        im.keys = [None] * ndir
-    from .common import capture_tag, param_epoch
+    im = getattr(w[0], '_ag_wih16', None)
+    if im is None or im.stack.shape != (ndir * H4, Fx) or im.stack.device != w[0].device:
+        im = w[0]._ag_wih16 = Bf16Images(ndir * H4, Fx, w[0].device)
     for d in range(ndir):
-        p_ = w[4 * d]
-        key = (capture_tag(p_.device), p_.data_ptr(), p_._version, param_epoch(p_))
-        if im.keys[d] != key:
-            K.to_bf16(p_.data[:, :Fx], out=stack[d * H4:(d + 1) * H4])
-            im.keys[d] = key
-    return stack
+        im.fill(d * H4, w[4 * d], Fx)
+    return im.stack
 
 
 class LSTMSeqFn(torch.autograd.Function):
@@ -102,7 +85,13 @@ class LSTMSeqFn(torch.autograd.Function):
 
     The static part is projected ONCE per clip (c @ W_ih[:, Fx:]^T + biases -> [B,4H]) and added inside the
     step kernel, instead of being concatenated to all T frames and multiplied T times; its weight / input
-    gradients come from the time sum of dgates (the same pass that gives the bias gradient)."""
+    gradients come from the time sum of dgates (the same pass that gives the bias gradient).
+
+    bf16 storage (x arrives as bfloat16): x, the layer output y, dgates' operand copy and dx are bfloat16 in HBM and every
+    large product runs on ag_gemm_h (ops._prod picks the kernel by its operands' dtype); gate pre-activations, cell states
+    and the persistent kernels' exchange stay fp32.  Storage decides the W_ih operand (the bf16 stack / the fp32 weight),
+    the dgates operand (one [T,B,ndir*4H] bf16 tensor the persistent launch writes beside its fp32 exchange buffer / that
+    buffer itself) and the form of dx (one product over both directions / one per direction); the rest is common."""
 
     @staticmethod
     def forward(ctx, x, lengths, ndir, static, *w):
@@ -113,47 +102,32 @@ class LSTMSeqFn(torch.autograd.Function):
         Fc = static.size(1) if static is not None else 0
         assert w[0].size(1) == Fx + Fc
         st = static.contiguous() if static is not None else None
-        # bf16 storage (x arrives as bfloat16): x, the layer output y, dgates' operand copy and dx are bfloat16 in HBM and
-        # every large product runs on ag_gemm_h; gate pre-activations, cell states and the persistent kernels' exchange stay
-        # fp32.  Needs the persistent launches (they write y / read dy as bf16).
         s16 = x.dtype == torch.bfloat16
-        if s16:
+        if s16:     # (the persistent launches write y / read dy as bf16)
             assert K.lstm_step_ok(B, H) and K.lstm_persist_ok(B, H, ndir, dev) and K.lstm_persist_bwd_ok(B, H, ndir, dev), \
                 'bf16 storage needs the persistent LSTM launches (modules.Discriminator.classify checks this)'
             wst = _wih16(w, ndir, Fx)
         y = torch.empty(T, B, ndir * H, device=dev, dtype=torch.bfloat16 if s16 else torch.float32)
         gates_all, c_all, whh, cbs = [], [], [], []
         fused = K.lstm_step_ok(B, H)
-        for d in range(ndir if s16 else 0):
+        for d in range(ndir):
             w_ih, w_hh, b_ih, b_hh = w[4 * d:4 * d + 4]
             g = torch.empty(T, B, 4 * H, device=dev)
-            wx16 = wst[d * 4 * H:(d + 1) * 4 * H]
-            if st is not None:
-                cb = torch.empty(B, 4 * H, device=dev)
-                K.gemm(st, w_ih.data[:, Fx:], cb, tb=True, bias=b_ih.data, res=_bcast_rows(b_hh.data, B))
-                _gh(x2, wx16, C=g.view(T * B, 4 * H), tb=True)
-                cbs.append(cb)
-            else:
-                _gh(x2, wx16, C=g.view(T * B, 4 * H), tb=True, bias=b_ih.data, res=_bcast_rows(b_hh.data, T * B))
-            gates_all.append(g)
-            c_all.append(torch.empty(T + 1, B, H, device=dev))
-            whh.append(w_hh.data.contiguous())
-        for d in range(0 if s16 else ndir):
-            w_ih, w_hh, b_ih, b_hh = w[4 * d:4 * d + 4]
-            g = torch.empty(T, B, 4 * H, device=dev)
+            g2 = g.view(T * B, 4 * H)
+            wx = wst[d * 4 * H:(d + 1) * 4 * H] if s16 else w_ih.data[:, :Fx]
             # b_ih + b_hh: one rides as the GEMM's bias, the other as a `res` whose row pitch is 0 (the same row for every
             # output row) - no launch to add the two vectors first
             if st is not None:
                 cb = torch.empty(B, 4 * H, device=dev)
                 K.gemm(st, w_ih.data[:, Fx:], cb, tb=True, bias=b_ih.data, res=_bcast_rows(b_hh.data, B))
                 if fused:
-                    K.gemm(x2, w_ih.data[:, :Fx], g.view(T * B, 4 * H), tb=True)
+                    _prod(x2, wx, g2, tb=True)
                     cbs.append(cb)
                 else:       # generic per-step path: fold the static term into the pre-activations up front
                     g.copy_(cb.unsqueeze(0).expand(T, B, 4 * H))
-                    K.gemm(x2, w_ih.data[:, :Fx], g.view(T * B, 4 * H), tb=True, beta=1.0)
+                    _prod(x2, wx, g2, tb=True, beta=1.0)
             else:
-                K.gemm(x2, w_ih.data, g.view(T * B, 4 * H), tb=True, bias=b_ih.data, res=_bcast_rows(b_hh.data, T * B))
+                _prod(x2, wx, g2, tb=True, bias=b_ih.data, res=_bcast_rows(b_hh.data, T * B))
             c = torch.empty(T + 1, B, H, device=dev)   # c[k+1] = cell after the k-th processed step
             if not (fused and K.lstm_persist_ok(B, H, ndir, dev)):
                 c[0].zero_()                           # (the persistent launch writes c_0 = 0 itself)
@@ -174,7 +148,7 @@ class LSTMSeqFn(torch.autograd.Function):
                         K.gemm(hp, whh[d], g[t], tb=True, beta=1.0)
                     K.lstm_cell_fwd(g[t], c[k], c[k + 1], h_out=hn, y_out=y[t, :, d * H:(d + 1) * H],
                                     h_prev=hp, valid=lengths, t=t)
-        ctx.ndir, ctx.has_len, ctx.has_static, ctx.s16 = ndir, lengths is not None, st is not None, s16
+        ctx.ndir, ctx.has_len, ctx.has_static = ndir, lengths is not None, st is not None
         ctx.params = w
         ctx.save_for_backward(x2, y, lengths if lengths is not None else x2.new_empty(0),
                               st if st is not None else x2.new_empty(0),
@@ -185,29 +159,32 @@ class LSTMSeqFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         T, B, Fx, H = ctx.shape
-        ndir = ctx.ndir
+        ndir, H4 = ctx.ndir, 4 * H
         sv = ctx.saved_tensors
-        x2, y = sv[0], sv[1]
+        x2, y2 = sv[0], sv[1].view(T * B, ndir * H)
         lengths = sv[2] if ctx.has_len else None
         st = sv[3] if ctx.has_static else None
         gates_all, c_all, w = list(sv[4:4 + ndir]), list(sv[4 + ndir:4 + 2 * ndir]), sv[4 + 2 * ndir:]
         dev = x2.device
+        s16 = x2.dtype == torch.bfloat16
         dy = dy.contiguous()
-        if ctx.s16:
-            return LSTMSeqFn._backward16(ctx, dy, x2, y, lengths, st, gates_all, c_all, w)
         whh = [w[4 * d + 1].contiguous() for d in range(ndir)]
-        dgs = [torch.empty(T, B, 4 * H, device=dev) for _ in range(ndir)]
-        dhb = [torch.empty(2, B, H, device=dev) for _ in range(ndir)]
-        dcb = [torch.empty(2, B, H, device=dev) for _ in range(ndir)]
+        dgs = [torch.empty(T, B, H4, device=dev) for _ in range(ndir)]
+        # (the persistent launch - all there is on bf16 storage - keeps dh / dc in its own exchange buffers)
+        dhb = None if s16 else [torch.empty(2, B, H, device=dev) for _ in range(ndir)]
+        dcb = None if s16 else [torch.empty(2, B, H, device=dev) for _ in range(ndir)]
+        dg16 = torch.empty(T, B, ndir * H4, device=dev, dtype=torch.bfloat16) if s16 else None
         wg = any(ctx.needs_input_grad[4:])
         need_ds = st is not None and ctx.needs_input_grad[3]
         # sum over time of dgates (the static input and the biases see every step's gradient): the persistent launch sums it
         # in the registers of the threads that produce dgates; other paths leave it to a pass over dgates below
         want_sum = st is not None and (wg or need_ds)
-        dgsums = [torch.empty(B, 4 * H, device=dev) for _ in range(ndir)] if want_sum else None
+        dgsums = [torch.empty(B, H4, device=dev) for _ in range(ndir)] if want_sum else None
         have_sum = False
-        if B <= 256 and H % 2 == 0:
-            have_sum = K.lstm_seq_bwd(gates_all, whh, c_all, dy, dgs, dhb, dcb, lengths, dgsum=dgsums)
+        if s16 or (B <= 256 and H % 2 == 0):
+            kw = dict(dg16=[dg16[:, :, d * H4:(d + 1) * H4] for d in range(ndir)]) if s16 else {}
+            have_sum = K.lstm_seq_bwd(gates_all, whh, c_all, dy, dgs, dhb, dcb, lengths, dgsum=dgsums, **kw)
+            assert have_sum or not (s16 and want_sum)
         else:
             for d in range(ndir):
                 g, c, dg = gates_all[d], c_all[d], dgs[d]
@@ -219,128 +196,59 @@ class LSTMSeqFn(torch.autograd.Function):
                                     dg[t], dcb[d][k & 1], dh_pass=dpass, valid=lengths, t=t)
                     if k > 0:
                         K.gemm(dg[t], whh[d], dpass, beta=1.0)
-        dx2 = torch.empty(T * B, Fx, device=dev)
-        outs = []
+        # dgates of direction d as the gradient products read them: rows in (t, b) order, [T*B, 4H]
+        dgo = [dg16.view(T * B, ndir * H4)[:, d * H4:(d + 1) * H4] if s16 else dgs[d].view(T * B, H4) for d in range(ndir)]
+        dx2 = None
+        if s16 and ctx.needs_input_grad[0]:
+            dx2 = torch.empty(T * B, Fx, device=dev, dtype=torch.bfloat16)
+            _prod(dg16.view(T * B, ndir * H4), _wih16(ctx.params, ndir, Fx), dx2)     # both directions in ONE product
+        elif not s16:
+            dx2 = torch.empty(T * B, Fx, device=dev)
         dstatic = torch.zeros_like(st) if need_ds else None
-        if dgsums is None:
-            dgsums = [None] * ndir
         for d in range(ndir):
             w_ih = w[4 * d]
-            wx = w_ih[:, :Fx] if st is not None else w_ih
-            dg2 = dgs[d].view(T * B, 4 * H)
-            K.gemm(dg2, wx, dx2, beta=0.0 if d == 0 else 1.0)
-            dgsum = dgsums[d]
-            if want_sum:
-                if not have_sum:
-                    # (read right below and by the weight-gradient products: complete at once, also inside a deferral scope)
-                    K.col_sum(dgs[d].view(T, B * 4 * H), dgsum.view(-1), accumulate=False, defer=False)
-                if need_ds:
-                    K.gemm(dgsum, w_ih[:, Fx:], dstatic, beta=1.0)
-        if not wg:
-            outs = [None] * (4 * ndir)
+            if not s16:
+                K.gemm(dgo[d], w_ih[:, :Fx], dx2, beta=0.0 if d == 0 else 1.0)
+            if want_sum and not have_sum:
+                # (read right below and by the weight-gradient products: complete at once, also inside a deferral scope)
+                K.col_sum(dgs[d].view(T, B * H4), dgsums[d].view(-1), accumulate=False, defer=False)
+            if need_ds:
+                K.gemm(dgsums[d], w_ih[:, Fx:], dstatic, beta=1.0)
+        outs = [] if wg else [None] * (4 * ndir)
         tgs = [[grad_target(p_) for p_ in ctx.params[4 * d:4 * d + 4]] for d in range(ndir)] if wg else []
         # every parameter gradient goes straight into ``.grad``: nothing reads it before the optimiser, so the second
         # stages of the split-K products and column sums below may wait for the enclosing scope's ONE launch
         direct_all = wg and all(t_ is not None for tg in tgs for t_ in tg)
-        import contextlib
         with (K.deferred_reduces() if direct_all else contextlib.nullcontext()):
             for d in range(ndir if wg else 0):
-                w_ih, w_hh = w[4 * d], w[4 * d + 1]
-                dg2 = dgs[d].view(T * B, 4 * H)
-                dgsum = dgsums[d]
-                tg = tgs[d]
+                w_ih, w_hh, tg = w[4 * d], w[4 * d + 1], tgs[d]
                 direct = all(t_ is not None for t_ in tg)
-                # h_prev of processing step k is the layer output of step k-1 (zero at padded steps,
-                # where dgates is zero as well)
                 if direct:      # accumulate straight into .grad
                     dw_ih, dw_hh = tg[0], tg[1]
                 else:
-                    dw_ih = torch.zeros_like(w_ih)
-                    dw_hh = torch.zeros_like(w_hh)
-                K.gemm(dg2, x2, dw_ih[:, :Fx] if st is not None else dw_ih, ta=True, beta=1.0, defer=direct_all)
+                    dw_ih, dw_hh = torch.zeros_like(w_ih), torch.zeros_like(w_hh)
+                _prod(dgo[d], x2, dw_ih[:, :Fx] if st is not None else dw_ih, ta=True, beta=1.0, defer=direct_all)
                 if st is not None:
-                    K.gemm(dgsum, st, dw_ih[:, Fx:], ta=True, beta=1.0, defer=direct_all)
+                    K.gemm(dgsums[d], st, dw_ih[:, Fx:], ta=True, beta=1.0, defer=direct_all)
                 if T > 1:
+                    # h_prev of processing step k is the layer output of step k-1 (zero at padded steps, where dgates is
+                    # zero as well): one time step earlier for the forward direction, one later for the reverse one
                     if d == 0:
-                        K.gemm(dgs[d][1:].view((T - 1) * B, 4 * H), y[:-1].view((T - 1) * B, ndir * H)[:, :H],
-                               dw_hh, ta=True, beta=1.0, defer=direct_all)
+                        _prod(dgo[d][B:], y2[:(T - 1) * B, :H], dw_hh, ta=True, beta=1.0, defer=direct_all)
                     else:
-                        K.gemm(dgs[d][:-1].view((T - 1) * B, 4 * H),
-                               y[1:].view((T - 1) * B, ndir * H)[:, H:2 * H], dw_hh, ta=True, beta=1.0, defer=direct_all)
-                src, rows = (dgsum, B) if dgsum is not None else (dg2, T * B)
+                        _prod(dgo[d][:(T - 1) * B], y2[B:, H:2 * H], dw_hh, ta=True, beta=1.0, defer=direct_all)
+                # (the bias sums read fp32 dgates on either storage)
+                src = dgsums[d] if want_sum else dgs[d].view(T * B, H4)
                 if direct:
-                    K.col_sum(src.view(rows, 4 * H), tg[2])
-                    K.col_sum(src.view(rows, 4 * H), tg[3])
+                    K.col_sum(src, tg[2])
+                    K.col_sum(src, tg[3])
                     outs += [None, None, None, None]
                     continue
-                db = torch.zeros(4 * H, device=dev)
-                K.col_sum(src.view(rows, 4 * H), db)
+                db = torch.zeros(H4, device=dev)
+                K.col_sum(src, db)
                 outs += [dw_ih, dw_hh, db, db.clone()]
-        dx = dx2.view(T, B, Fx) if ctx.needs_input_grad[0] else None
+        dx = dx2.view(T, B, Fx) if (dx2 is not None and ctx.needs_input_grad[0]) else None
         return (dx, None, None, dstatic) + tuple(outs)
-
-
-def _lstm_backward16(ctx, dy, x2, y, lengths, st, gates_all, c_all, w):
-    """LSTMSeqFn.backward on bf16 storage: dy, x2, y are bfloat16; the persistent launch leaves dgates in fp32 (its exchange
-    buffer) AND as one bfloat16 tensor [T,B,ndir*4H], the operand of the three gradient products (ag_gemm_h)"""
-    T, B, Fx, H = ctx.shape
-    ndir = ctx.ndir
-    dev = x2.device
-    H4 = 4 * H
-    whh = [w[4 * d + 1].contiguous() for d in range(ndir)]
-    dgs = [torch.empty(T, B, H4, device=dev) for _ in range(ndir)]
-    dg16 = torch.empty(T, B, ndir * H4, device=dev, dtype=torch.bfloat16)
-    wg = any(ctx.needs_input_grad[4:])
-    need_ds = st is not None and ctx.needs_input_grad[3]
-    want_sum = st is not None and (wg or need_ds)
-    dgsums = [torch.empty(B, H4, device=dev) for _ in range(ndir)] if want_sum else None
-    have_sum = K.lstm_seq_bwd(gates_all, whh, c_all, dy, dgs, None, None, lengths, dgsum=dgsums,
-                              dg16=[dg16[:, :, d * H4:(d + 1) * H4] for d in range(ndir)])
-    assert have_sum or not want_sum
-    dg2 = dg16.view(T * B, ndir * H4)
-    dx2 = None
-    if ctx.needs_input_grad[0]:
-        dx2 = torch.empty(T * B, Fx, device=dev, dtype=torch.bfloat16)
-        _gh(dg2, _wih16(w, ndir, Fx), C16=dx2)            # both directions in ONE product (K = ndir * 4H)
-    dstatic = torch.zeros_like(st) if need_ds else None
-    for d in range(ndir if need_ds else 0):
-        K.gemm(dgsums[d], w[4 * d][:, Fx:], dstatic, beta=1.0)
-    outs = []
-    if not wg:
-        outs = [None] * (4 * ndir)
-    tgs = [[grad_target(p_) for p_ in ctx.params[4 * d:4 * d + 4]] for d in range(ndir)] if wg else []
-    direct_all = wg and all(t_ is not None for tg in tgs for t_ in tg)
-    import contextlib
-    with (K.deferred_reduces() if direct_all else contextlib.nullcontext()):
-        for d in range(ndir if wg else 0):
-            w_ih, w_hh = w[4 * d], w[4 * d + 1]
-            tg = tgs[d]
-            direct = all(t_ is not None for t_ in tg)
-            dw_ih, dw_hh = (tg[0], tg[1]) if direct else (torch.zeros_like(w_ih), torch.zeros_like(w_hh))
-            dgd = dg2[:, d * H4:(d + 1) * H4]
-            _gh(dgd, x2, C=dw_ih[:, :Fx] if st is not None else dw_ih, ta=True, beta=1.0, defer=direct_all)
-            if st is not None:
-                K.gemm(dgsums[d], st, dw_ih[:, Fx:], ta=True, beta=1.0, defer=direct_all)
-            if T > 1:
-                y2 = y.view(T * B, ndir * H)
-                if d == 0:
-                    _gh(dgd[B:], y2[:(T - 1) * B, :H], C=dw_hh, ta=True, beta=1.0, defer=direct_all)
-                else:
-                    _gh(dgd[:(T - 1) * B], y2[B:, H:2 * H], C=dw_hh, ta=True, beta=1.0, defer=direct_all)
-            src, rows = (dgsums[d], B) if want_sum else (dgs[d].view(T * B, H4), T * B)
-            if direct:
-                K.col_sum(src.view(rows, H4), tg[2])
-                K.col_sum(src.view(rows, H4), tg[3])
-                outs += [None, None, None, None]
-                continue
-            db = torch.zeros(H4, device=dev)
-            K.col_sum(src.view(rows, H4), db)
-            outs += [dw_ih, dw_hh, db, db.clone()]
-    dx = dx2.view(T, B, Fx) if dx2 is not None else None
-    return (dx, None, None, dstatic) + tuple(outs)
-
-
-LSTMSeqFn._backward16 = staticmethod(_lstm_backward16)
 
 
 # --------------------------------------------------------------------------------------
@@ -372,6 +280,35 @@ def _front_pre(zc, wz, b_ih, b_hh, pre, gru):
         K.gemm(zc2, wz, pre2, tb=True, bias=bias)
     else:
         K.gemm(zc2, wz, pre2, tb=True, bias=b_ih, res=_bcast_rows(b_hh, T * B))
+
+
+def _stop_head_grads(ds, h2, dws, i, **sum_kw):
+    """the stop head's part of a front's backward, s_t = h_t W_s^T + b_s: returns ds [B,T] as rows in (t, b) order [T*B,1]
+    and, when ``dws`` is given, leaves dW_s = ds^T h in dws[i] and db_s = sum ds in dws[i + 1] (``sum_kw``: col_sum's)"""
+    ds_tb = ds.t().contiguous().view(-1, 1)
+    if dws is not None:
+        K.gemm(ds_tb, h2, dws[i], ta=True)
+        K.col_sum(ds_tb, dws[i + 1], **sum_kw)
+    return ds_tb
+
+
+def _ext_grads(ds_tb, sw, dx, T, B, S):
+    """the external gradients of a persistent front backward (ag_gfront_bwd), read where they are: dL/dh_t (the stop
+    head's, if any) from a [T,B,S] product, dL/dx_t from the trunk's gradient (any row pitch: channel 0 of its slab) - no
+    [T,B,S+fs] staging tensor to fill and copy into"""
+    dh_ext = None
+    if ds_tb is not None:
+        dh_ext = torch.empty(T, B, S, device=ds_tb.device)
+        K.gemm(ds_tb, sw, dh_ext.view(T * B, S))
+    return dh_ext, dx if (dx is None or dx.stride(1) == 1) else dx.contiguous()
+
+
+def _xprev_rows(x, xt, T, B, fs):
+    """x_{t-1} for t = 1..T-1 as rows in (t, b) order, the operand of the W_ih[:, :fs] gradient: the persistent forward left
+    the frames time-major (xt); otherwise a transposed copy of x [B, T*fs]"""
+    if xt is not None:
+        return xt[:T - 1].view((T - 1) * B, fs)
+    return x.view(B, T, fs)[:, :T - 1].transpose(0, 1).contiguous().view((T - 1) * B, fs)
 
 
 class GFront(object):
@@ -455,10 +392,7 @@ class GFrontFn(torch.autograd.Function):
         # projection at frame t, and (top layer) the stopper head
         dha = [torch.zeros(T, B, S, device=dev) for _ in range(nl)]
         if ds is not None:
-            ds_tb = ds.t().contiguous().view(T * B, 1)
-            if dws is not None:
-                K.gemm(ds_tb, hs[-1].view(T * B, S), dws[4 * nl + 2], ta=True)
-                K.col_sum(ds_tb, dws[4 * nl + 3])
+            ds_tb = _stop_head_grads(ds, hs[-1].view(T * B, S), dws, 4 * nl + 2)
             K.gemm(ds_tb, sw, dha[-1].view(T * B, S))
         dgs = [torch.empty(T, B, 4 * S, device=dev) for _ in range(nl)]
         dxt = torch.empty(T, B, fs, device=dev)      # d(pre-tanh) of the projection, per frame
@@ -486,23 +420,12 @@ class GFrontFn(torch.autograd.Function):
         fused step (ag_lstm_front_bwd_step)."""
         dev = x.device
         persist = T > 0 and wx.stride(1) == 1 and K.gfront_bwd_persist_ok(B, S, fs, dev)
-        ds_tb = None
-        if ds is not None:
-            ds_tb = ds.t().contiguous().view(T * B, 1)
-            if dws is not None:
-                K.gemm(ds_tb, hs.view(T * B, S), dws[4 * nl + 2], ta=True)
-                K.col_sum(ds_tb, dws[4 * nl + 3], defer=False)
+        ds_tb = _stop_head_grads(ds, hs.view(T * B, S), dws, 4 * nl + 2, defer=False) if ds is not None else None
         dgs = torch.empty(T, B, 4 * S, device=dev)
         dxt = torch.empty(T, B, fs, device=dev)
         if persist:
-            # the whole loop in ONE launch, [W_hh | W_x] and W_p resident in registers (ag_gfront_bwd).  The external
-            # gradients are read where they are: dL/dx_t from the trunk's gradient (any row pitch: channel 0 of its slab),
-            # dL/dh_t (the stop head's, if any) from a [T,B,S] product - no [T,B,S+fs] staging tensor to fill and copy into
-            dh_ext = None
-            if ds_tb is not None:
-                dh_ext = torch.empty(T, B, S, device=dev)
-                K.gemm(ds_tb, sw, dh_ext.view(T * B, S))
-            dx_ext = dx if (dx is None or dx.stride(1) == 1) else dx.contiguous()
+            # the whole loop in ONE launch, [W_hh | W_x] and W_p resident in registers (ag_gfront_bwd)
+            dh_ext, dx_ext = _ext_grads(ds_tb, sw, dx, T, B, S)
             K.gfront_bwd_persist(gates, cs, x, dh_ext, dx_ext, w_hh, wx, pw, dgs, dxt)
             return [dgs], dxt
         dacc = torch.zeros(T, B, S + fs, device=dev)
@@ -544,9 +467,7 @@ class GFrontFn(torch.autograd.Function):
             # frozen): s_t = h_t W_s^T + b_s, so only dW_s = ds^T h and db_s = sum ds are wanted - no frame loop
             dws = [None] * len(items)
             dws[4 * nl + 2], dws[4 * nl + 3] = _zeros_like_list([items[4 * nl + 2]['v'], items[4 * nl + 3]['v']])
-            ds_tb = ds.t().contiguous().view(T * B, 1)
-            K.gemm(ds_tb, hs[-1].view(T * B, S), dws[4 * nl + 2], ta=True)
-            K.col_sum(ds_tb, dws[4 * nl + 3])
+            _stop_head_grads(ds, hs[-1].view(T * B, S), dws, 4 * nl + 2)
             return (None, None) + tuple(front.group.backward(dws))
         dws = front.group.zero_dws() if wg else None
         # (the persistent launch takes frame sizes the fused per-frame step does not: any multiple of 8 up to its panel width)
@@ -571,10 +492,8 @@ class GFrontFn(torch.autograd.Function):
                 if l == 0:
                     K.gemm(dg2, zc.contiguous().view(T * B, Fz), dwih[:, fs:], ta=True, defer=True)
                     if T > 1:
-                        # x_{t-1} rows in (t, b) order: the persistent forward left them time-major (xt)
-                        xprev = xt[:T - 1].view((T - 1) * B, fs) if xt is not None else \
-                            x.view(B, T, fs)[:, :T - 1].transpose(0, 1).contiguous().view((T - 1) * B, fs)
-                        K.gemm(dgs[0][1:].view((T - 1) * B, 4 * S), xprev, dwih[:, :fs], ta=True, defer=True)
+                        K.gemm(dgs[0][1:].view((T - 1) * B, 4 * S), _xprev_rows(x, xt, T, B, fs), dwih[:, :fs], ta=True,
+                               defer=True)
                 else:
                     K.gemm(dg2, hs[l - 1].view(T * B, S), dwih, ta=True, defer=True)
                 if T > 1:
@@ -662,23 +581,17 @@ class GRUFrontFn(torch.autograd.Function):
         dgi = torch.empty(T, B, 3 * S, device=dev)
         dgh = torch.empty(T, B, 3 * S, device=dev)
         dxt = torch.empty(T, B, fs, device=dev)
-        dh_ext = None
-        if not persist:
+        ds_tb = _stop_head_grads(ds, hs[1:].view(T * B, S), dws, 6, defer=False) if ds is not None else None
+        if persist:
+            # the whole loop in ONE launch (ag_gfront_bwd)
+            dh_ext, dx_ext = _ext_grads(ds_tb, sw, dx, T, B, S)
+            K.grufront_bwd_persist(gi, hs, gh, x, dh_ext, dx_ext, w_hh, wx, pw, dgi, dgh, dxt)
+        else:
             dxa = dx.contiguous().clone() if dx is not None else torch.zeros(B, T * fs, device=dev)
             dha = torch.zeros(T + 1, B, S, device=dev)     # dha[t+1] accumulates dL/dh_t
-        if ds is not None:
-            ds_tb = ds.t().contiguous().view(T * B, 1)
-            if wg:
-                K.gemm(ds_tb, hs[1:].view(T * B, S), dws[6], ta=True)
-                K.col_sum(ds_tb, dws[7], defer=False)
-            if persist:
-                dh_ext = torch.empty(T, B, S, device=dev)
-            K.gemm(ds_tb, sw, dh_ext.view(T * B, S) if persist else dha[1:].view(T * B, S))
-        if persist:
-            # the whole loop in ONE launch (ag_gfront_bwd); the external gradients dL/dh_t, dL/dx_t are read in place
-            dx_ext = dx if (dx is None or dx.stride(1) == 1) else dx.contiguous()
-            K.grufront_bwd_persist(gi, hs, gh, x, dh_ext, dx_ext, w_hh, wx, pw, dgi, dgh, dxt)
-        dh_dir = None if persist else torch.empty(B, S, device=dev)
+            if ds_tb is not None:
+                K.gemm(ds_tb, sw, dha[1:].view(T * B, S))
+            dh_dir = torch.empty(B, S, device=dev)
         for t in reversed(range(0 if persist else T)):
             gx = dxt[t]
             K.act_bwd2d(dxa[:, t * fs:(t + 1) * fs], x[:, t * fs:(t + 1) * fs], gx, ACT_TANH)
@@ -694,9 +607,7 @@ class GRUFrontFn(torch.autograd.Function):
             K.col_sum(dxt2, dws[5])
             K.gemm(dgi2, zc.contiguous().view(T * B, Fz), dws[0][:, fs:], ta=True)
             if T > 1:
-                xprev = xt[:T - 1].view((T - 1) * B, fs) if xt is not None else \
-                    x.view(B, T, fs)[:, :T - 1].transpose(0, 1).contiguous().view((T - 1) * B, fs)
-                K.gemm(dgi[1:].view((T - 1) * B, 3 * S), xprev, dws[0][:, :fs], ta=True)
+                K.gemm(dgi[1:].view((T - 1) * B, 3 * S), _xprev_rows(x, xt, T, B, fs), dws[0][:, :fs], ta=True)
             K.gemm(dgh2, hs[:T].view(T * B, S), dws[1], ta=True)
             K.col_sum(dgi2, dws[2])
             K.col_sum(dgh2, dws[3])

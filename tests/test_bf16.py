@@ -504,3 +504,38 @@ def test_critic_sequence_path_bf16_storage_vs_fp32_storage(K, bf16):
         if k.split('.')[-1].startswith('bias') and k.endswith('_v'):
             continue
         close_bf16(p1[k], p0[k], k, elem=1.0, l2=0.15)
+
+
+def test_lstm_bf16_storage_reads_the_current_weights_after_every_update(K, bf16):
+    """LSTMSeqFn on bf16 storage at the smallest shape the persistent launches take (H 64: grids of 16 and 4 workgroups), six
+    iterations, ragged lengths.  Run A keeps ONE set of Parameters and overwrites all of them with fresh values before every
+    iteration; run B builds new Parameters from clones of the same values, so no kept bf16 image of W_ih can serve it.  A
+    stale image (of the previous iteration's weights, 0.1-scale noise replaced by other 0.1-scale noise) is a gross error,
+    not a rounding one: y, dx and every parameter gradient must be EQUAL."""
+    from audiogan_amd import ops
+    T, B, Fx, H, ndir = 6, 8, 64, 64, 2
+    dev = torch.device('cuda')
+    assert K.lstm_step_ok(B, H) and K.lstm_persist_ok(B, H, ndir, dev) and K.lstm_persist_bwd_ok(B, H, ndir, dev)
+    gen = torch.Generator().manual_seed(91)
+    lens = torch.tensor([6, 3, 5, 1, 6, 2, 4, 5]).cuda()
+    shapes = [(4 * H, Fx), (4 * H, H), (4 * H,), (4 * H,)] * ndir
+    kept = [torch.nn.Parameter(torch.zeros(s).cuda()) for s in shapes]
+    for it in range(6):
+        vals = [(torch.randn(s, generator=gen) * 0.1).cuda() for s in shapes]
+        x = torch.randn(T, B, Fx, generator=gen).cuda().to(torch.bfloat16)
+        gy = torch.randn(T, B, ndir * H, generator=gen).cuda().to(torch.bfloat16)
+        with torch.no_grad():
+            for p, v in zip(kept, vals):
+                p.copy_(v)
+        got = []
+        for w in (kept, [torch.nn.Parameter(v.clone()) for v in vals]):
+            for p in w:
+                p.grad = None
+            xx = x.clone().requires_grad_(True)
+            y = ops.LSTMSeqFn.apply(xx, lens, ndir, None, *w)
+            y.backward(gy)
+            got.append([y.detach(), xx.grad] + [p.grad for p in w])
+        assert K.lstm_persist_status() == 0
+        assert got[0][0].dtype == torch.bfloat16 and got[0][1].dtype == torch.bfloat16 and float(got[0][0].abs().max()) > 0
+        for i, (a, b) in enumerate(zip(*got)):
+            assert torch.equal(a, b), (it, i, float((a.float() - b.float()).abs().max()))

@@ -357,3 +357,129 @@ def test_abi_13_and_last_kernel_is_empty_on_a_fresh_thread():
     t.start()
     t.join()
     assert seen == [b'']
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# bf16 images of the biLSTM's W_ih (recurrent._wih16): they belong to the layer's first weight Parameter
+# ---------------------------------------------------------------------------------------------------------------------
+def _wih16_setup(monkeypatch, ndir=2, H=8, Fx=8, Fc=3):
+    from audiogan_amd import kernels as K
+    calls = []
+
+    def to_bf16(src, out=None):
+        calls.append(tuple(src.shape))
+        if out is None:
+            return src.to(torch.bfloat16)
+        out.copy_(src)
+        return out
+
+    monkeypatch.setattr(K, 'to_bf16', to_bf16)
+    gen = torch.Generator().manual_seed(17)
+    w = []
+    for _ in range(ndir):
+        w += [torch.nn.Parameter(torch.randn(*s, generator=gen)) for s in ((4 * H, Fx + Fc), (4 * H, H), (4 * H,), (4 * H,))]
+    want = lambda: torch.cat([w[4 * d].data[:, :Fx] for d in range(ndir)]).bfloat16()  # noqa: E731
+    return w, calls, want
+
+
+def test_wih16_image_follows_its_parameter(monkeypatch):
+    """the stack is cat(W_ih[:, :Fx]) of the CURRENT weights after an in-place update (version) and after a write through
+    .data (epoch); unchanged weights convert nothing"""
+    from audiogan_amd import recurrent as R
+    from audiogan_amd.common import bump_param_epoch
+    w, calls, want = _wih16_setup(monkeypatch)
+    st = R._wih16(w, 2, 8)
+    assert st.shape == (64, 8) and st.dtype == torch.bfloat16 and torch.equal(st, want()) and len(calls) == 2
+    assert R._wih16(w, 2, 8) is st and len(calls) == 2
+    with torch.no_grad():
+        w[0].mul_(-1.5)
+        w[4].add_(1.0)
+    assert torch.equal(R._wih16(w, 2, 8), want()) and len(calls) == 4
+    w[4].data.copy_(torch.randn(32, 11))
+    bump_param_epoch([w[4]])
+    assert torch.equal(R._wih16(w, 2, 8), want()) and len(calls) == 5         # (only the direction that changed)
+    assert R._wih16(w, 2, 8) is st and len(calls) == 5
+
+
+def test_wih16_images_die_with_their_parameter_and_stay_out_of_checkpoints(monkeypatch):
+    """deleting the Parameters releases the images; a state_dict (what checkpoint.save writes) carries no attributes, and a
+    pickle of the Parameter itself stores None in the holder's place"""
+    import gc
+    import pickle
+    import weakref
+    from audiogan_amd import recurrent as R
+    w, calls, want = _wih16_setup(monkeypatch)
+    st = R._wih16(w, 2, 8)
+    assert pickle.loads(pickle.dumps(w[0]))._ag_wih16 is None
+    assert all(torch.is_tensor(v) and not hasattr(v, '_ag_wih16') for v in torch.nn.ParameterList(w).state_dict().values())
+    ref = weakref.ref(st)
+    del st, w, want
+    gc.collect()
+    assert ref() is None
+
+
+def test_wih16_eight_rounds_as_the_autograd_block_calls_it(monkeypatch):
+    """forward-time call, backward-time call (with the block's Parameters, ctx.params - not the ``.data`` aliases it saved,
+    which are fresh objects of version 0 on every backward), update: after every call the stack matches the current
+    weights, and a round converts each direction ONCE - the backward reuses the forward's image"""
+    from audiogan_amd import recurrent as R
+    from audiogan_amd.common import bump_param_epoch
+    w, calls, want = _wih16_setup(monkeypatch)
+    seen = []
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, *ws):
+            ctx.params = ws
+            ctx.save_for_backward(*[t_.data for t_ in ws])
+            seen.append(torch.equal(R._wih16(ws, 2, 8), want()))
+            return x * 2
+
+        @staticmethod
+        def backward(ctx, dy):
+            assert all(s_ is not p_ and s_._version == 0 for s_, p_ in zip(ctx.saved_tensors, ctx.params))
+            seen.append(torch.equal(R._wih16(ctx.params, 2, 8), want()))
+            return (dy * 2,) + (None,) * len(ctx.params)
+
+    x = torch.ones(3, requires_grad=True)
+    gen = torch.Generator().manual_seed(18)
+    for it in range(8):
+        n0 = len(calls)
+        Fn.apply(x, *w).sum().backward()
+        assert len(calls) - n0 == 2, (it, len(calls) - n0)
+        for p in w:
+            new = torch.randn(p.shape, generator=gen)
+            if it % 2:                       # the fused optimiser's way: raw writes + epoch
+                p.data.copy_(new)
+            else:                            # torch's way: an in-place op moves the version
+                with torch.no_grad():
+                    p.copy_(new)
+        if it % 2:
+            bump_param_epoch(w)
+    assert seen == [True] * 16
+
+
+def test_broadcast_parameters_bumps_the_epoch(monkeypatch):
+    """ddp.broadcast_parameters writes through ``.data`` (no version moves): it bumps the parameters' epoch, so a WNGroup
+    that was up to date materialises the received weights"""
+    import torch.distributed as dist
+    from audiogan_amd import ddp, kernels as K
+    from audiogan_amd.common import WNGroup
+    n = []
+    fwd = K.weight_norm_fwd
+    monkeypatch.setattr(K, 'weight_norm_fwd', lambda ents: (n.append(len(ents)), fwd(ents))[1])
+    mod = torch.nn.Module()
+    mod.v, mod.g = torch.nn.Parameter(torch.randn(6, 5)), torch.nn.Parameter(torch.rand(6, 1) + 0.5)
+    grp = WNGroup()
+    grp.add(mod.v, mod.g)
+    w0 = grp.prepare()[0].w.clone()
+    grp.prepare()
+    assert n == [1]
+    monkeypatch.setattr(dist, 'is_available', lambda: True)
+    monkeypatch.setattr(dist, 'is_initialized', lambda: True)
+    monkeypatch.setattr(dist, 'get_world_size', lambda group=None: 2)
+    monkeypatch.setattr(dist, 'broadcast', lambda flat, src=0, group=None: flat.mul_(2.0))     # "rank 0's weights"
+    ddp.broadcast_parameters(mod)
+    w1 = grp.prepare()[0].w
+    assert n == [1, 1]
+    np.testing.assert_allclose(w1.numpy(), 2 * w0.numpy(), rtol=1e-6)
