@@ -51,6 +51,10 @@ class OptDesc(C.Structure):
     _fields_ = [('p', vp), ('grad', vp), ('s1', vp), ('s2', vp), ('n', i64)]
 
 
+class EmaDesc(C.Structure):
+    _fields_ = [('ema', vp), ('p', vp), ('n', i64)]
+
+
 SUMMARY_COLS = 16
 
 
@@ -149,6 +153,8 @@ SIGNATURES = {
     'ag_axpby': (C.c_int, [vp, vp, i64, f32, f32, vp]),
     'ag_grad_norms': (C.c_int, [vp, C.c_int, vp, vp, vp, f32, vp, C.c_int, vp]),
     'ag_opt_step': (C.c_int, [vp, C.c_int, vp, C.c_int, f32, f32, f32, f32, f32, f32, C.c_int, vp, vp, vp, vp, vp, vp]),
+    'ag_ema_chunk': (C.c_int, []),
+    'ag_ema_update': (C.c_int, [vp, C.c_int, vp, C.c_int, f32, C.c_int, vp, C.c_int, C.c_int, vp]),
     'ag_logit_summary': (C.c_int, [vp, i64, i64, vp, C.c_int, vp, C.c_int, C.c_int, vp]),
     'ag_sqnorm_rows': (C.c_int, [vp, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
     'ag_vec_stats': (C.c_int, [vp, f32, vp, C.c_int, vp]),

@@ -2,7 +2,9 @@
 but as ``state_dict``s instead of whole-module pickles, so they load into this package's modules AND
 into the reference's (the parameter names are identical, see tests/test_host_logic.py).  Optimiser
 state, step counters and RNG state -- which the reference never saved -- go
-into a fifth file ``%s-opt-%05d``.
+into a fifth file ``%s-opt-%05d``.  With an ``optim.EMA`` its state goes into that file too, and the averaged generator /
+Embedder weights are written as two more plain state_dicts, ``%s-genema-%05d`` and ``%s-egema-%05d`` (``load(...,
+use_ema=True)`` reads them in place of ``gen`` / ``eg``: the inference user's one-liner).
 
 ``load`` also reads the REFERENCE's own files: those hold whole-module pickles (``T.save(d, ...)``, audiogan.py:936-939,
 read back with ``T.load`` at :698-701); their ``state_dict()`` is taken (unpickling them needs the reference's classes
@@ -39,7 +41,10 @@ def _plain(x, where='extra'):
                     '(the file must load with weights_only=True)' % (where, type(x).__name__))
 
 
-def save(prefix, iteration, d=None, g=None, e_g=None, e_d=None, opt_d=None, opt_g=None, extra=None):
+_EMA_ROLES = {'gen': 'genema', 'eg': 'egema'}
+
+
+def save(prefix, iteration, d=None, g=None, e_g=None, e_d=None, opt_d=None, opt_g=None, extra=None, ema=None):
     extra = _plain(extra)
     mods = dict(d=d, g=g, e_g=e_g, e_d=e_d)
     written = []
@@ -48,11 +53,17 @@ def save(prefix, iteration, d=None, g=None, e_g=None, e_d=None, opt_d=None, opt_
         if m is not None:
             torch.save({k: v.detach().cpu() for k, v in m.state_dict().items()}, _path(prefix, role, iteration))
             written.append(_path(prefix, role, iteration))
-    if opt_d is not None or opt_g is not None or extra is not None:
+            if ema is not None and role in _EMA_ROLES:
+                torch.save({k: v.detach().cpu() for k, v in ema.module_state_dict(m).items()},
+                           _path(prefix, _EMA_ROLES[role], iteration))
+                written.append(_path(prefix, _EMA_ROLES[role], iteration))
+    if opt_d is not None or opt_g is not None or extra is not None or ema is not None:
         blob = dict(opt_d=_cpu(opt_d.state_dict()) if opt_d is not None else None,
                     opt_g=_cpu(opt_g.state_dict()) if opt_g is not None else None,
                     extra=extra, torch_rng=torch.get_rng_state(),
                     cuda_rng=torch.cuda.get_rng_state_all() if torch.cuda.is_available() else None)
+        if ema is not None:
+            blob['ema'] = _cpu(ema.state_dict())
         torch.save(blob, _path(prefix, 'opt', iteration))
         written.append(_path(prefix, 'opt', iteration))
     return written
@@ -75,8 +86,11 @@ def _read(path, allow_pickle):
 
 
 def load(prefix, iteration, d=None, g=None, e_g=None, e_d=None, opt_d=None, opt_g=None, strict=True, restore_rng=None,
-         allow_pickle=False):
-    """``restore_rng``: None = restore the RNG streams when an optimiser is being restored (a resumed training run), leave
+         allow_pickle=False, ema=None, use_ema=False):
+    """``ema``: an ``optim.EMA`` to restore from the ``opt`` file, after the optimisers (a file written without one raises
+    ``KeyError``; with ``strict=False`` the EMA is reset to the loaded parameters instead, with a warning).  ``use_ema``:
+    ``g`` / ``e_g`` receive the AVERAGED weights (the ``genema`` / ``egema`` files).
+    ``restore_rng``: None = restore the RNG streams when an optimiser is being restored (a resumed training run), leave
     them alone for inference-only loads; True / False force it.  Returns ``extra``; ``load.last_rng`` says what happened
     to the RNG state ('restored', 'cpu only ...', 'not restored')."""
     import warnings
@@ -84,17 +98,28 @@ def load(prefix, iteration, d=None, g=None, e_g=None, e_d=None, opt_d=None, opt_
     for role, key in _ROLES:
         m = mods[key]
         if m is not None:
-            obj = _read(_path(prefix, role, iteration), allow_pickle)
+            obj = _read(_path(prefix, _EMA_ROLES.get(role, role) if use_ema else role, iteration), allow_pickle)
             sd = obj.state_dict() if isinstance(obj, torch.nn.Module) else obj      # reference-style module pickle
             m.load_state_dict(sd, strict=strict)
     extra = None
     load.last_rng = 'not restored'
     p = _path(prefix, 'opt', iteration)
-    if os.path.exists(p):
-        blob = _read(p, allow_pickle)
+    blob = _read(p, allow_pickle) if os.path.exists(p) else None
+    if blob is not None:
         for o, key in ((opt_d, 'opt_d'), (opt_g, 'opt_g')):
             if o is not None and blob.get(key) is not None:
                 o.load_state_dict(_to(blob[key], o.params[0].device))
+    if ema is not None:
+        if blob is not None and blob.get('ema') is not None:
+            ema.load_state_dict(_to(blob['ema'], ema.params[0].device))
+        elif strict:
+            raise KeyError('checkpoint.load: %s holds no EMA state (it was saved without ema=...); strict=False starts the '
+                           'average again from the loaded parameters' % p)
+        else:
+            warnings.warn('audiogan_amd.checkpoint.load: %s holds no EMA state: the average restarts from the loaded '
+                          'parameters' % p)
+            ema.reset()
+    if blob is not None:
         if restore_rng is None:
             restore_rng = opt_d is not None or opt_g is not None
         if restore_rng:

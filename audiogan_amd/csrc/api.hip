@@ -24,7 +24,9 @@ extern "C" const char* ag_last_kernel(void) { return g_kernel; }
 // the front's persistent launches, process-wide deferral with pause / resume, ag_build_zc, ag_critic_batch; v10 - bf16 storage: ag_gemm_h, bf16 in / out flags of the transposes, rowdot, col_sum and the
 // persistent LSTM launches; v11 - the generation mode of the fronts;
 // v12 - ag_last_kernel; v13 - the fronts' persistent launches take argument structs: ag_gfront_fwd, ag_gfront_bwd):
-// audiogan_amd/_lib.py refuses a library of another version, so Python that relies on a new mode can never drive an older build
+// audiogan_amd/_lib.py refuses a library of another version, so Python that relies on a new mode can never drive an older build.
+// Still v13 with ag_ema_update / ag_ema_chunk: an ADDED entry point changes no existing call, and a library without it is
+// refused when _lib.py binds the missing symbol at import
 extern "C" int ag_abi_version(void) { return 13; }
 extern "C" const char* ag_arch(void) { return "gfx950"; }
 extern "C" const char* ag_last_error(void) { return g_err; }

@@ -600,6 +600,83 @@ extern "C" int ag_opt_step(const ag_opt_desc* descs_dev, int n, const float* nor
 }
 
 // ------------------------------------------------------------------------------------------
+// exponential moving average of a parameter list (contract: include/audiogan_hip.h).  This pass moves 12 bytes per
+// element and nothing else, so the grid is 1-D over EMA_CHUNK-element chunks of the tensors (map: chunk -> tensor, chunk
+// inside it): a one-element bias costs one workgroup, not a row of idle ones as under opt_step_kernel's (256, n) grid.
+// ------------------------------------------------------------------------------------------
+#define EMA_CHUNK 4096
+#define EMA_VPT (EMA_CHUNK / 4 / 256)      // 16-byte accesses per thread and tensor in a full chunk
+
+__device__ __forceinline__ float ema_one(float e, float p, float w) { return w == 1.f ? p : fmaf(w, p - e, e); }
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const ag_ema_desc* __restrict__ descs, int n_tensors,
+                                                         const int32_t* __restrict__ map, float decay, int warmup,
+                                                         const int32_t* __restrict__ step_dev, int step0, int k_host) {
+  const int ti = map[2 * (int64_t)blockIdx.x], ci = map[2 * (int64_t)blockIdx.x + 1];
+  if ((unsigned)ti >= (unsigned)n_tensors || ci < 0) return;      // (a map entry that names no tensor moves nothing)
+  const ag_ema_desc d = descs[ti];
+  const int64_t s = (int64_t)ci * EMA_CHUNK;
+  if (s >= d.n) return;
+  float dc = decay;
+  if (warmup) {
+    // the counter was advanced by an earlier launch on this stream: one value for every workgroup of this one
+    const int k = step_dev ? step_dev[0] - step0 : k_host;
+    const float kf = (float)(k > 0 ? k : 0);
+    dc = fminf(decay, (1.f + kf) / (10.f + kf));
+  }
+  const float w = 1.f - dc;
+  const int len = (int)(d.n - s < EMA_CHUNK ? d.n - s : EMA_CHUNK);
+  float* e = d.ema + s;                    // (EMA_CHUNK * 4 bytes is a multiple of 16: a chunk is aligned as its tensor is)
+  const float* p = d.p + s;
+  int head = len, nv = 0;                  // differently aligned pointers: element by element
+  if ((((uintptr_t)e ^ (uintptr_t)p) & 15) == 0) {
+    head = (int)(((16 - ((uintptr_t)e & 15)) & 15) >> 2);
+    if (head > len) head = len;
+    nv = (len - head) >> 2;
+  }
+  f32x4* e4 = reinterpret_cast<f32x4*>(e + head);
+  const f32x4* p4 = reinterpret_cast<const f32x4*>(p + head);
+  if (nv == EMA_CHUNK / 4) {
+    // a full aligned chunk (nearly all of the traffic): every load of the thread is issued before the first use
+    f32x4 ev[EMA_VPT], pv[EMA_VPT];
+#pragma unroll
+    for (int j = 0; j < EMA_VPT; ++j) {
+      ev[j] = e4[threadIdx.x + 256 * j];
+      pv[j] = p4[threadIdx.x + 256 * j];
+    }
+#pragma unroll
+    for (int j = 0; j < EMA_VPT; ++j) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) ev[j][c] = ema_one(ev[j][c], pv[j][c], w);
+      e4[threadIdx.x + 256 * j] = ev[j];
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < nv; i += 256) {
+    f32x4 ev = e4[i];
+    const f32x4 pv = p4[i];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ev[c] = ema_one(ev[c], pv[c], w);
+    e4[i] = ev;
+  }
+  for (int i = threadIdx.x; i < head; i += 256) e[i] = ema_one(e[i], p[i], w);
+  for (int i = head + 4 * nv + threadIdx.x; i < len; i += 256) e[i] = ema_one(e[i], p[i], w);
+}
+
+extern "C" int ag_ema_chunk(void) { return EMA_CHUNK; }
+
+extern "C" int ag_ema_update(const ag_ema_desc* descs_dev, int n, const int32_t* map_dev, int nchunks, float decay, int warmup,
+                             const int32_t* step_dev, int step0, int k, void* stream) {
+  AG_REQUIRE(descs_dev && map_dev && n > 0 && nchunks >= n, "ag_ema_update: bad args (every tensor has at least one chunk)");
+  AG_REQUIRE(decay >= 0.f && decay <= 1.f, "ag_ema_update: decay must lie in [0, 1], got %g", (double)decay);
+  AG_REQUIRE(step_dev || k >= 0, "ag_ema_update: without a device step counter the host k must be >= 0");
+  hipLaunchKernelGGL(ema_update_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, map_dev, decay,
+                     warmup, step_dev, step0, k);
+  AG_CHECK_LAUNCH("ag_ema_update");
+  return AG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // GRU cell pointwise (BASELINE config C4; torch.nn.GRUCell semantics, gate order r|z|n):
 //   r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r * gh_n), h' = (1-z) n + z h
 // gi = x W_ih^T + b_ih, gh = h W_hh^T + b_hh are complete on entry.  fwd overwrites gi with the

@@ -831,6 +831,64 @@ def opt_step(params, grads, s1, s2, norms, kind, lr, clip, grad_scale, a1, b2, e
 
 
 # ------------------------------------------------------------------------------------
+# exponential moving average of a parameter list (optim.EMA)
+# ------------------------------------------------------------------------------------
+EMA_CHUNK = int(lib.ag_ema_chunk())
+_ema_plans = OrderedDict()       # (shadow ptr, param ptr, numel) per tensor -> plan
+
+
+def ema_plan(shadows, params):
+    """-> (bytes, chunks, tensors): the checked descriptors followed by the chunk-to-tensor map ([chunks][2] int32: tensor,
+    chunk inside it), built once per list of tensors.  The bytes go through ``_table`` on every ``ema_update``, so the
+    device copy is cached / pinned under capture exactly as the optimiser's table is.  A caller that keeps its tensors
+    (optim.EMA) may keep the plan and hand it back: the per-tensor checks then run once, not per launch."""
+    import numpy as np
+    assert len(shadows) == len(params) and len(params) > 0
+    for e, p in zip(shadows, params):
+        _chk(e, 'shadow'); _chk(p, 'param')
+        assert e.is_contiguous() and p.is_contiguous() and e.numel() == p.numel() >= 1, (tuple(e.shape), tuple(p.shape))
+        assert e.device == p.device == params[0].device
+    sig = tuple((e.data_ptr(), p.data_ptr(), p.numel()) for e, p in zip(shadows, params))
+    plan = _ema_plans.get(sig)
+    if plan is not None:
+        _ema_plans.move_to_end(sig)
+        return plan
+    descs = [_lib.EmaDesc(*t) for t in sig]
+    counts = np.asarray([(t[2] + EMA_CHUNK - 1) // EMA_CHUNK for t in sig], dtype=np.int64)
+    total = int(counts.sum())
+    assert total < 2 ** 31
+    cmap = np.empty((total, 2), dtype=np.int32)
+    cmap[:, 0] = np.repeat(np.arange(len(counts)), counts)
+    cmap[:, 1] = np.arange(total) - np.repeat(np.cumsum(counts) - counts, counts)
+    plan = (b''.join(bytes(d) for d in descs) + cmap.tobytes(), total, len(sig))
+    _ema_plans[sig] = plan
+    while len(_ema_plans) > 64:
+        _ema_plans.popitem(last=False)
+    return plan
+
+
+def ema_update(shadows, params, decay, warmup, step_dev, step0, k=0, plan=None):
+    """shadows[i] = lerp(shadows[i], params[i], 1 - d) for the whole list in ONE launch (ag_ema_update): per element
+    ``e = fmaf(1 - d, p - e, e)`` in fp32; d = decay, or with ``warmup`` min(decay, (1 + k) / (10 + k)) where
+    k = max(0, step_dev[0] - step0) (``step_dev``: the optimiser's int32 device step counter, only read) or the host ``k``
+    when ``step_dev`` is None.  Tensors: fp32, contiguous, any numel >= 1, any 4-byte alignment; ``params`` are not
+    written.  ``plan``: what ``ema_plan(shadows, params)`` returned for these very tensors."""
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError('audiogan_amd: ema_update needs 0 <= decay <= 1, got %r' % (decay,))
+    _chk(step_dev, 'step_dev', torch.int32)
+    raw, chunks, n = plan if plan is not None else ema_plan(shadows, params)
+    assert n == len(params) == len(shadows)
+    tab = _table('ema', [raw], params[0].device)
+    check(lib.ag_ema_update(_p(tab), n, C.c_void_p(tab.data_ptr() + n * C.sizeof(_lib.EmaDesc)), chunks, decay,
+                            int(bool(warmup)), _p(step_dev), int(step0), int(k), _stream()), 'ag_ema_update')
+
+
+def _work_ema(shadows, params, *a_, **kw):
+    return 'ema_update_kernel', 0.0, 12.0 * sum(p.numel() for p in params)
+
+
+# ------------------------------------------------------------------------------------
 # per-kernel timing hook for bench.py's roofline figure: HIP events recorded on the launch
 # stream around the launches of ONE kernel class (or all of them in the discovery pass).
 # ------------------------------------------------------------------------------------
@@ -932,7 +990,7 @@ for _n, _w in (('gemm', _work_gemm), ('conv_engine', _work_conv), ('conv_wgrad',
                ('channel_sum', None), ('leaky_bwd', None), ('col_sum', None), ('lstm_cell_fwd', None),
                ('lstm_cell_bwd', None), ('weight_norm_fwd', None), ('weight_norm_bwd', None),
                ('bce_logits_fwd', None), ('bce_logits_bwd', None), ('act_fwd', None), ('act_bwd', None),
-               ('axpby', None), ('grad_norms', None), ('opt_step', None)):
+               ('axpby', None), ('grad_norms', None), ('opt_step', None), ('ema_update', _work_ema)):
     _instrument(_n, _w)
 
 

@@ -32,6 +32,7 @@ one of the eager warm-up iterations of a capture - commits the reference's scala
 host read: a captured loop logs like an eager one).  The loop drains the ring every ``summary_every`` iterations, at the end of
 ``run()`` and before every checkpoint; a drain raises on NaN / |g| > 1e5 gradients and on a persistent launch that gave up
 (``check_grad``, :786, :909), so a bad run stops and its state is never saved."""
+import contextlib
 import os
 import time
 
@@ -46,7 +47,7 @@ class TrainLoop(object):
                  critic_iter=100, require_acc=0.5, gencatchup=1, dgradclip=1.0, ggradclip=0.1, g_optim='boundary_seeking',
                  checkpoint_every=500, checkpoint_prefix=None, fixed_critic_iter=None, stop=None, check=True, graphed=False,
                  host=None, sample_every=0, sample_words=None, sample_z=None, sample_seed=0, on_sample=None, sample_dir=None,
-                 audio_every=500, summary=None, summary_every=None):
+                 audio_every=500, summary=None, summary_every=None, ema=None, sample_ema=True):
         """``loader``: the generator ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths, keys, cseq,
         clen], dataset.py:91); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
         (``dataset.pick_words(..., skip_samples=True)[1:3]``, audiogan.py:715-716); ``stop``: None = Bernoulli stop draws
@@ -62,7 +63,12 @@ class TrainLoop(object):
         stop draws are kept in ``last_sample_u``.
 
         ``summary``: a ``summary.Summary`` that receives one row per executed iteration (None: no iteration launches or logs
-        anything more than before); ``summary_every``: drain it every so many iterations (default: half its capacity)."""
+        anything more than before); ``summary_every``: drain it every so many iterations (default: half its capacity).
+
+        ``ema``: an ``optim.EMA`` over ``opt_g`` (None: no call, launch or allocation more than before).  Every executed
+        generator iteration - eager, replayed, or an eager warm-up iteration of a capture - is followed by exactly one
+        ``ema.update()`` (in a captured loop: one kernel node of the generator graph, behind the optimiser's); checkpoints carry it.
+        ``sample_ema``: samples are drawn with the averaged weights (``ema.applied()``) instead of the last iterate."""
         self.g, self.d, self.e_g, self.e_d, self.opt_g, self.opt_d = g, d, e_g, e_d, opt_g, opt_d
         self.loader, self.pick_words = loader, pick_words
         self.B, self.maxlen, self.dev = batch_size, maxlen, torch.device(device)
@@ -72,6 +78,7 @@ class TrainLoop(object):
         self.fixed_critic_iter, self.stop, self.check = fixed_critic_iter, stop, check
         self.dis_iter = self.gen_iter = 0
         self.summary = summary
+        self.ema, self.sample_ema = ema, bool(sample_ema)
         self.summary_every = None if summary is None else max(1, int(summary_every or max(1, summary.capacity // 2)))
         self._since_drain = 0
         self.baseline = None
@@ -186,6 +193,8 @@ class TrainLoop(object):
             r = train.g_step_full(self.g, self.d, self.e_g, self.e_d, self.opt_g, st['real'], st['real_len'], st['wcs'], st['wcl'],
                                   st['z'], st['n1'], st['n2'], st['n3'], 'never', 'never', st['baseline'], self.ggradclip,
                                   self.g_optim, check=False, host=False, **self._summary_kw())
+            if self.ema is not None:
+                self.ema.update()           # (its table exists: the warm-up iterations made it)
             st['baseline'].copy_(r['baseline'])           # the running baseline lives on the device, updated by the graph
             self._out['g'] = r
 
@@ -251,7 +260,8 @@ class TrainLoop(object):
         cs, cl = self._sample_words
         cs = cs.to(self.dev).long() if torch.is_tensor(cs) else self._up(cs, torch.long)
         cl = cl.to(self.dev).long() if torch.is_tensor(cl) else self._up(cl, torch.long)
-        with torch.no_grad():
+        averaged = self.ema.applied() if (self.ema is not None and self.sample_ema) else contextlib.nullcontext()
+        with torch.no_grad(), averaged:
             u = torch.rand(self.nframes, self.B, device=self.dev, generator=self._sample_rng)
             self.last_sample_u = u
             wave, _, stop_list, length = self.g.generate(self.e_g(cs, cl), z=self.sample_z, u=u)
@@ -311,7 +321,11 @@ class TrainLoop(object):
             b = self.baseline
             checkpoint.save(self.prefix, self.gen_iter, d=self.d, g=self.g, e_g=self.e_g, e_d=self.e_d, opt_d=self.opt_d,
                             opt_g=self.opt_g, extra=dict(dis_iter=self.dis_iter, gen_iter=self.gen_iter,
-                                                         baseline=float(b) if b is not None else None))
+                                                         baseline=float(b) if b is not None else None),
+                            **self._ema_kw())
+
+    def _ema_kw(self):
+        return dict(ema=self.ema) if self.ema is not None else {}
 
     def g_iteration(self):
         if self.graphed:
@@ -335,6 +349,8 @@ class TrainLoop(object):
                               self._noise(), self._noise(), self._stop_arg(self.nframes), self._stop_arg(self.nframes),
                               self.baseline, self.ggradclip, self.g_optim, check=self.check, host=self.host,
                               **self._summary_kw(gen_iter=self.gen_iter))
+        if self.ema is not None:
+            self.ema.update()
         self.baseline = r['baseline']
         self._summary_tick()
         self._maybe_checkpoint()
@@ -371,7 +387,7 @@ class TrainLoop(object):
     def resume(self, iteration):
         """load the checkpoint written at generator iteration ``iteration`` (audiogan.py:696-701) and continue from there"""
         extra = checkpoint.load(self.prefix, iteration, d=self.d, g=self.g, e_g=self.e_g, e_d=self.e_d, opt_d=self.opt_d,
-                                opt_g=self.opt_g) or {}
+                                opt_g=self.opt_g, **self._ema_kw()) or {}
         self.dis_iter, self.gen_iter = int(extra.get('dis_iter', 0)), int(extra.get('gen_iter', iteration))
         self.baseline = extra.get('baseline', None)
         if self.graphed and self._graphs is not None and self.baseline is not None:

@@ -3,7 +3,13 @@
 Replaces ``check_grad`` (audiogan.py:232-240), ``clip_grad`` (:243-253) and
 ``T.optim.RMSprop(...).step()`` (:693-694, :788, :921); Adam follows the TF defaults of the
 obsolete graph (computation_graph.py:58-59), which equal torch.optim.Adam's.
+
+``EMA`` (beyond the reference, like Adam): an exponential moving average of an optimiser's parameters, updated by one
+launch per step (``kernels.ema_update``) that reads the optimiser's device step counter, so it runs inside a captured
+generator iteration and its warm-up decay moves on every replay.
 """
+import contextlib
+
 import torch
 
 from . import kernels as K
@@ -148,6 +154,118 @@ class Adam(_Fused):
         K.opt_step(ps, gs, s1, s2, norms, K.OPT_ADAM, self.lr, float(clip), float(gscale),
                    self.betas[0], self.betas[1], self.eps, self.step_count, self._state['step'], part=part,
                    norm_sum=self._state['norm_sum'], flags=self._state['flags'])
+
+
+class EMA(object):
+    """Exponential moving average of ``opt.params`` (for ``opt_g``: the generator AND its Embedder, so a sample uses a
+    consistent pair).  After every optimiser step, ``update()`` sets, per element in fp32,
+
+        e = fmaf(1 - d, p - e, e),    d = min(decay, (1 + k) / (10 + k)) with ``warmup`` (else d = decay),
+
+    k = the optimiser's steps since construction / ``reset()`` (read from its DEVICE counter by the kernel).  The lerp form
+    is exact when p == e: a parameter that never receives a gradient keeps an average bit-identical to itself.
+
+    ``step0`` is a host integer: an ``update()`` captured into a hipGraph keeps the one of its capture (capture after
+    ``reset()`` / ``load_state_dict``, or re-capture).
+
+    Ranks that hold identical parameters hold identical averages: nothing is all-reduced; call ``reset()`` after
+    ``ddp.broadcast_parameters``."""
+
+    def __init__(self, opt, decay=0.999, warmup=True):
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError('EMA: decay must lie in [0, 1], got %r' % (decay,))
+        self.opt, self.params = opt, opt.params
+        self.decay, self.warmup = decay, bool(warmup)
+        self._applied = False
+        self._flat, self.shadows = self._flat_like()
+        self._raw = None                 # (flat buffer, views): the raw parameters while ``applied()`` is active
+        self._ptrs = self._pviews = self._plan = None
+        self.step0 = 0
+        self.reset()
+
+    def _flat_like(self):
+        offs, n = common.flat_offsets([p.numel() for p in self.params])          # every view 16-byte aligned
+        flat = torch.zeros(n, device=self.params[0].device, dtype=torch.float32)
+        return flat, [flat[o:o + p.numel()] for p, o in zip(self.params, offs)]
+
+    def _flat_params(self):
+        """the parameters' storage as 1-D views, made again (with the launch plan) only when a parameter's storage moved"""
+        ptrs = [p.data_ptr() for p in self.params]
+        if ptrs != self._ptrs:
+            self._ptrs, self._pviews, self._plan = ptrs, [p.data.view(-1) for p in self.params], None
+        return self._pviews
+
+    def _opt_step(self):
+        self.opt._ensure()
+        return int(self.opt._state['step'].item())
+
+    def _idle(self, what):
+        if self._applied:
+            raise RuntimeError('EMA.%s: the averaged weights are applied to the parameters (inside EMA.applied())' % what)
+
+    def reset(self):
+        """the averages become the current parameters and the warm-up starts again at the optimiser's current step"""
+        self._idle('reset')
+        with torch.no_grad():
+            torch._foreach_copy_(self.shadows, self._flat_params())
+        self.step0 = self._opt_step()
+
+    def update(self):
+        """one launch on the current stream (eager or under capture); call it after ``opt.step()``"""
+        self._idle('update')
+        self.opt._ensure()
+        ps = self._flat_params()
+        if self._plan is None:
+            self._plan = K.ema_plan(self.shadows, ps)          # (the per-tensor checks and the chunk map: once)
+        K.ema_update(self.shadows, ps, self.decay, self.warmup, self.opt._state['step'], self.step0, plan=self._plan)
+
+    @contextlib.contextmanager
+    def applied(self):
+        """inference with the averaged weights: inside the block the parameters HOLD the averages, afterwards (also when
+        the block raises) their raw values again, bit for bit.  The values are copied, never the ``.data`` pointers:
+        captured graphs, descriptor tables and the weight caches all hold the parameters' addresses.  The parameter epoch
+        is bumped both ways, so weight-norm materialisations and bf16 weight images are rebuilt on entry and on exit.
+        Not re-entrant; refused while a stream is capturing."""
+        self._idle('applied')
+        if self.params[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('EMA.applied: not while a stream is capturing (the copies would become graph nodes)')
+        if self._raw is None:
+            self._raw = self._flat_like()
+        raw, ps = self._raw[1], self._flat_params()
+        self._applied = True
+        try:
+            with torch.no_grad():
+                torch._foreach_copy_(raw, ps)
+                torch._foreach_copy_(ps, self.shadows)
+            common.bump_param_epoch(self.params)
+            yield self
+        finally:
+            with torch.no_grad():
+                torch._foreach_copy_(ps, raw)
+            common.bump_param_epoch(self.params)
+            self._applied = False
+
+    def module_state_dict(self, module):
+        """``module.state_dict()`` with every tracked parameter replaced by its average (everything else as the module has
+        it): loads with ``strict=True`` wherever the module's own state_dict does"""
+        avg = {id(p): s for p, s in zip(self.params, self.shadows)}
+        sd = module.state_dict()
+        for name, p in module.named_parameters():
+            if id(p) in avg and name in sd:
+                sd[name] = avg[id(p)].detach().clone().view(p.shape)
+        return sd
+
+    def state_dict(self):
+        return dict(decay=self.decay, warmup=self.warmup, step0=self.step0, shadows=[s.clone() for s in self.shadows])
+
+    def load_state_dict(self, sd):
+        self._idle('load_state_dict')
+        assert len(sd['shadows']) == len(self.shadows), (len(sd['shadows']), len(self.shadows))
+        self.decay, self.warmup, self.step0 = float(sd['decay']), bool(sd['warmup']), int(sd['step0'])
+        with torch.no_grad():
+            for a, b in zip(self.shadows, sd['shadows']):
+                a.copy_(b.reshape(-1))
 
 
 def make_optimizer(params, kind, lr):

@@ -584,6 +584,31 @@ int ag_opt_step(const ag_opt_desc* descs_dev, int n, const float* norms, int kin
                 void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Exponential moving average of a parameter list (beyond the reference, like Adam): one launch for the whole list.
+ *   per element, fp32:  e = fmaf(1 - d, p - e, e)      (the lerp form: exact when p == e; 1 - d == 1 stores p itself)
+ *   d = decay                                 when warmup == 0
+ *   d = min(decay, (1 + k) / (10 + k))        otherwise, in fp32, the same value in every workgroup;
+ *       k = max(0, step_dev[0] - step0) with the optimiser's device step counter (read only: ag_grad_norms incremented
+ *       it in an EARLIER launch on the same stream, so every workgroup reads one value), or the host value `k` when
+ *       step_dev is NULL - as ag_opt_step does with `step`.  A captured launch therefore warms up on every replay.
+ * `p` and the counter are never written; no workspace, no atomics, no host sync.
+ * Grid: one workgroup per chunk of ag_ema_chunk() consecutive elements of one tensor.  map_dev is the chunk-to-tensor
+ * map, [nchunks][2] int32 = (tensor index, chunk index inside that tensor), tensor i contributing
+ * ceil(n_i / ag_ema_chunk()) entries; the caller builds it once and keeps it in device memory with the descriptors.
+ * A tensor whose two pointers are equally aligned modulo 16 bytes moves in 16-byte accesses between a scalar head and
+ * tail; any other tensor moves element by element.  Pointers are 4-byte aligned, every n >= 1, 0 <= decay <= 1.
+ * ------------------------------------------------------------------------- */
+typedef struct ag_ema_desc {
+  float* ema;
+  const float* p;
+  int64_t n;
+} ag_ema_desc;
+
+int ag_ema_chunk(void);
+int ag_ema_update(const ag_ema_desc* descs_dev, int n, const int32_t* map_dev, int nchunks, float decay, int warmup,
+                  const int32_t* step_dev, int step0, int k, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-iteration summaries (audiogan.py:776-809, :875-884, :911-920: the scalars the reference logs) computed on the
  * device and gathered into a ring the host reads whenever it wants (audiogan_amd/summary.py).  Every reduction sums in
  * a fixed order (no float atomics): two runs give the same bits.
