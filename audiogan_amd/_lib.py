@@ -159,6 +159,9 @@ SIGNATURES = {
     'ag_sqnorm_rows': (C.c_int, [vp, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
     'ag_vec_stats': (C.c_int, [vp, f32, vp, C.c_int, vp]),
     'ag_summary_commit': (C.c_int, [vp, vp]),
+    'ag_ltas_ws_numel': (i64, [C.c_int, C.c_int]),
+    'ag_ltas_power': (C.c_int, [vp, i64, vp, vp, vp, C.c_int, C.c_int, vp]),
+    'ag_score_accum': (C.c_int, [vp, i64, i64, vp, f32, C.c_int, vp, C.c_int, C.c_int, vp]),
 }
 
 

@@ -1850,3 +1850,49 @@ def _work_named(*a_, **kw):
 
 for _n in ('logit_summary', 'sqnorm_rows', 'vec_stats', 'summary_commit'):
     _instrument(_n, _work_named)
+
+
+# ------------------------------------------------------------------------------------
+# held-out evaluation (evaluate.Evaluator): long-term average spectrum of ragged clips, running critic statistics
+# ------------------------------------------------------------------------------------
+LTAS_BINS = 129          # bins 0..128 of the 256-point DFT
+SCORE_WORDS = 6
+
+
+def ltas_power(x, lens, out=None, nframes=None):
+    """x [B, L] (unit stride along L, any row pitch), lens int64 [B] or None -> out [B, 129] fp32: per clip the mean over its
+    frames (256 samples, hop 128, periodic Hann; a clip shorter than one frame is ONE zero-padded frame) of the power
+    |X[k]|^2 of the 256-point DFT, k = 0..128.  ``nframes``: an int32 [B] tensor that receives the frame counts.  Samples at
+    or past ``lens`` are never read.  Returns ``out``; the logarithm is the caller's (ag_ltas_power)."""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64); _chk(nframes, 'nframes', torch.int32)
+    assert x.dim() == 2, tuple(x.shape)
+    B, L = x.shape
+    ld = _rows(x, 'x', B, L)
+    assert lens is None or (lens.is_contiguous() and lens.numel() == B)
+    assert nframes is None or (nframes.is_contiguous() and nframes.numel() == B)
+    if out is None:
+        out = torch.empty(B, LTAS_BINS, dtype=torch.float32, device=x.device)
+    _chk(out, 'out')
+    assert out.is_contiguous() and tuple(out.shape) == (B, LTAS_BINS), tuple(out.shape)
+    _bind_ws(int(lib.ag_ltas_ws_numel(B, L)), x.device)         # (both launches are enqueued before the call returns)
+    check(lib.ag_ltas_power(_p(x), ld, _p(lens), _p(out), _p(nframes), B, L, _stream()), 'ag_ltas_power')
+    return out
+
+
+def score_accum(cls, nframes, target, positive, acc):
+    """one critic output cls [B, T'] (fp32, any strides) ADDED to ``acc``, six float64 device words the caller zeroes once per
+    evaluation: clips with a valid frame, sum_b of the per-clip mean BCE towards ``target``, valid frames, hits among them
+    (cls > 0 if ``positive`` else cls < 0), sum cls, sum cls^2 over the valid frames (ag_score_accum: one launch, sums in
+    double, masked entries never read)."""
+    _chk(cls, 'cls'); _chk(nframes, 'nframes', torch.int64); _chk(acc, 'acc', torch.float64)
+    assert cls.dim() == 2, tuple(cls.shape)
+    B, T = cls.shape
+    assert nframes is None or (nframes.is_contiguous() and nframes.numel() == B)
+    assert acc.is_contiguous() and acc.numel() == SCORE_WORDS, tuple(acc.shape)
+    check(lib.ag_score_accum(_p(cls), cls.stride(0), cls.stride(1), _p(nframes), float(target), int(bool(positive)), _p(acc),
+                             B, T, _stream()), 'ag_score_accum')
+    return acc
+
+
+for _n in ('ltas_power', 'score_accum'):
+    _instrument(_n, _work_named)

@@ -31,7 +31,11 @@ Summaries (:776-809, :875-884, :911-920): with ``summary=summary.Summary(...)`` 
 one of the eager warm-up iterations of a capture - commits the reference's scalars to a row of the summary's device ring (no
 host read: a captured loop logs like an eager one).  The loop drains the ring every ``summary_every`` iterations, at the end of
 ``run()`` and before every checkpoint; a drain raises on NaN / |g| > 1e5 gradients and on a persistent launch that gave up
-(``check_grad``, :786, :909), so a bad run stops and its state is never saved."""
+(``check_grad``, :786, :909), so a bad run stops and its state is never saved.
+
+Held-out evaluation (beyond the reference): with ``evaluator=evaluate.Evaluator(...)`` and ``eval_every`` > 0, every
+``eval_every``-th generator iteration is followed by one eager pass over the evaluator's fixed held-out set (critic loss and
+accuracy on unseen real clips and on fakes, feature penalty, spectral distance); the results collect in ``eval_log``."""
 import contextlib
 import os
 import time
@@ -47,7 +51,7 @@ class TrainLoop(object):
                  critic_iter=100, require_acc=0.5, gencatchup=1, dgradclip=1.0, ggradclip=0.1, g_optim='boundary_seeking',
                  checkpoint_every=500, checkpoint_prefix=None, fixed_critic_iter=None, stop=None, check=True, graphed=False,
                  host=None, sample_every=0, sample_words=None, sample_z=None, sample_seed=0, on_sample=None, sample_dir=None,
-                 audio_every=500, summary=None, summary_every=None, ema=None, sample_ema=True):
+                 audio_every=500, summary=None, summary_every=None, ema=None, sample_ema=True, evaluator=None, eval_every=0):
         """``loader``: the generator ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths, keys, cseq,
         clen], dataset.py:91); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
         (``dataset.pick_words(..., skip_samples=True)[1:3]``, audiogan.py:715-716); ``stop``: None = Bernoulli stop draws
@@ -68,7 +72,14 @@ class TrainLoop(object):
         ``ema``: an ``optim.EMA`` over ``opt_g`` (None: no call, launch or allocation more than before).  Every executed
         generator iteration - eager, replayed, or an eager warm-up iteration of a capture - is followed by exactly one
         ``ema.update()`` (in a captured loop: one kernel node of the generator graph, behind the optimiser's); checkpoints carry it.
-        ``sample_ema``: samples are drawn with the averaged weights (``ema.applied()``) instead of the last iterate."""
+        ``sample_ema``: samples are drawn with the averaged weights (``ema.applied()``) instead of the last iterate.
+
+        ``evaluator``: an ``evaluate.Evaluator`` (None: no call, launch or allocation more than before); after every generator
+        iteration with ``gen_iter % eval_every == 0``, behind the sample, ``evaluator.run(gen_iter, dis_iter)`` scores its fixed
+        held-out set and the result dict is appended to ``eval_log``.  In a captured loop the pass runs eagerly between two
+        replays, exactly as sampling does; it changes no training bit.  One pass over 4 held-out minibatches of the
+        training batch size (8 critic forwards, 4 generations) costs 0.4 - 0.5 of a captured training pass (README,
+        profiles/eval_pass.txt): evaluate every few hundred generator iterations, not every one."""
         self.g, self.d, self.e_g, self.e_d, self.opt_g, self.opt_d = g, d, e_g, e_d, opt_g, opt_d
         self.loader, self.pick_words = loader, pick_words
         self.B, self.maxlen, self.dev = batch_size, maxlen, torch.device(device)
@@ -79,6 +90,7 @@ class TrainLoop(object):
         self.dis_iter = self.gen_iter = 0
         self.summary = summary
         self.ema, self.sample_ema = ema, bool(sample_ema)
+        self.evaluator, self.eval_every, self.eval_log = evaluator, int(eval_every or 0), []
         self.summary_every = None if summary is None else max(1, int(summary_every or max(1, summary.capacity // 2)))
         self._since_drain = 0
         self.baseline = None
@@ -275,6 +287,14 @@ class TrainLoop(object):
                 write_wav(os.path.join(self.sample_dir, 'sample-%05d-%d.wav' % (n, i)), w[i, :int(ln[i])])
         return wave, length, stop_list
 
+    # ---- held-out evaluation (evaluate.Evaluator) ----------------------------------------------------
+    def _maybe_evaluate(self):
+        if self.evaluator is None or self.eval_every <= 0 or self.gen_iter % self.eval_every != 0:
+            return None
+        r = self.evaluator.run(gen_iter=self.gen_iter, dis_iter=self.dis_iter)
+        self.eval_log.append(r)
+        return r
+
     # ---- summaries ------------------------------------------------------------------------
     def _summary_kw(self, **kw):
         """the iterations' extra arguments (none without a summary: the calls are then exactly what they were)"""
@@ -340,6 +360,7 @@ class TrainLoop(object):
             self._summary_tick()
             self._maybe_checkpoint()
             self._maybe_sample()
+            self._maybe_evaluate()
             return self._out['g']
         self.gen_iter += 1
         real, real_len, _, _ = self._real()
@@ -355,6 +376,7 @@ class TrainLoop(object):
         self._summary_tick()
         self._maybe_checkpoint()
         self._maybe_sample()
+        self._maybe_evaluate()
         return r
 
     def outer(self):

@@ -407,6 +407,20 @@ class Discriminator(nn.Module):
         date); features() / classify() called on their own prepare their block at its first use"""
         prepare_groups([self._stack.group, self._head.group])
 
+    def refresh_weights(self):
+        """the twin of ``Generator.refresh_weights``: materialise the weight-normed weights of the conv stack and the heads
+        NOW, whatever the cache says, and forget the bfloat16 images of the biLSTM's W_ih (``_ag_wih16``; the heads' ``w16``
+        images go with their materialisation).  A captured optimiser step rewrites the parameters through raw pointers and
+        bumps neither their versions nor their epochs: an eager forward between two replays would otherwise find its old
+        cache keys "current".  (Re-materialising unchanged parameters writes the same bits.)"""
+        for gr in (self._stack.group, self._head.group):
+            gr._key = None
+        for p in self.rnn.parameters():
+            im = getattr(p, '_ag_wih16', None)
+            if im is not None:
+                im.keys.clear()
+        self.prepare_weights()
+
     def forward(self, x, length, c, percent_used=0.1, lens_all=None):
         self.prepare_weights()
         acts, lens_list = self.features(x, length, lens_all)

@@ -647,6 +647,39 @@ int ag_sqnorm_rows(const float* gx, int64_t ld, const int64_t* nframes_i64, floa
 int ag_vec_stats(const float* v, float sign, float* out2, int n, void* stream);
 int ag_summary_commit(const ag_summary_desc* desc_dev, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Held-out evaluation (audiogan_amd/evaluate.py; beyond the reference, which never scores its validation data): the
+ * long-term average spectrum of ragged clips and the running statistics of a critic output.  Fixed-order sums, no atomics:
+ * two runs give the same bits.
+ *   ag_ltas_power    x [B, L] fp32 of row pitch ldx (elements), unit column stride; n_b = clamp(lens[b], 0, L) (lens NULL:
+ *                    L).  Frames of 256 samples, hop 128, periodic Hann window w[i] = 0.5 - 0.5 cos(2 pi i / 256): with
+ *                    n_b >= 256 the frames j = 0 .. (n_b - 256) / 128, each wholly inside the clip (a tail shorter than
+ *                    a hop is not covered); otherwise ONE frame, the clip followed by zeros.
+ *                    out[b, k], k = 0..128 ([B, 129] contiguous) = mean over the clip's frames of |X_j[k]|^2, X_j the
+ *                    256-point DFT of the windowed frame - the power itself, no logarithm; nframes_out[b] (int32, may be
+ *                    NULL) = the frame count.  x[b, t] is never read for t >= n_b: padding may hold anything.  Window and
+ *                    twiddles are cospif values of exact arguments; fp32 sums.  A clip of more than 16 frames is spread
+ *                    over workgroups whose partial sums go to a bound workspace of ag_ltas_ws_numel(B, L) floats
+ *                    (ag_bind_workspace; 0: none needed) and are added in ascending frame order by a second launch.
+ *   ag_score_accum   x [B, T] logits of any (row, column) pitch in elements (sxb, sxt); n_b = clamp(nframes[b], 0, T)
+ *                    (NULL: T).  ADDS to acc, six doubles the caller zeroes once per evaluation:
+ *                      acc[0] += the number of clips with n_b >= 1
+ *                      acc[1] += sum_b (sum_{t < n_b} bce(x[b,t], target)) / n_b    (audiogan.py:191-192, per element in fp32)
+ *                      acc[2] += sum_b n_b
+ *                      acc[3] += the valid entries with x > 0 (positive != 0) or x < 0 (positive == 0)
+ *                      acc[4] += sum of x, acc[5] += sum of x^2, over the valid entries
+ *                    so loss = acc[1] / acc[0], accuracy = acc[3] / acc[2], mean = acc[4] / acc[2] and
+ *                    std = sqrt(max(0, acc[5] / acc[2] - mean^2)).  UNLIKE ag_logit_summary, whose mean / std run over all
+ *                    B*T entries as the reference's numpy calls do, these run over the VALID entries only; masked
+ *                    entries are never read.  One workgroup, every sum in double, one lane updates acc with plain loads
+ *                    and stores; B*T <= 2^22.
+ * ------------------------------------------------------------------------- */
+int64_t ag_ltas_ws_numel(int B, int L);
+int ag_ltas_power(const float* x, int64_t ldx, const int64_t* lens_i64, float* out, int32_t* nframes_out, int B, int L,
+                  void* stream);
+int ag_score_accum(const float* x, int64_t sxb, int64_t sxt, const int64_t* nframes_i64, float target, int positive,
+                   double* acc, int B, int T, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
