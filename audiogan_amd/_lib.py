@@ -41,6 +41,16 @@ class FrontFwdArgs(C.Structure):
         'ws')] + [(n, i64) for n in ('ldx', 'lds', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
 
 
+FRONT_MAX_LAYERS = 8
+
+
+class FrontStackArgs(C.Structure):
+    _fields_ = [('struct_bytes', i64), ('gen', i32), ('nl', i32)] + [(n, vp * FRONT_MAX_LAYERS) for n in (
+        'gates', 'hs', 'cs', 'w_hh', 'w_in', 'bias')] + [(n, vp) for n in (
+        'w_p', 'b_p', 'x', 'xt', 'w_s', 'b_s', 'u', 's', 'first', 't_run', 'ws')] + [
+        (n, i64) for n in ('ldx', 'lds', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
+
+
 class FrontBwdArgs(C.Structure):
     _fields_ = [('struct_bytes', i64), ('cell', i32), ('pad_', i32)] + [(n, vp) for n in (
         'ga', 'state', 'gh', 'x', 'dh_ext', 'dx_ext', 'w_hh', 'w_x', 'w_p', 'dgs', 'dgh', 'dxt', 'ws')] + [
@@ -132,6 +142,9 @@ SIGNATURES = {
     'ag_gfront_bwd_persist_ok': (C.c_int, [C.c_int] * 4),
     'ag_gfront_fwd': (C.c_int, [C.POINTER(FrontFwdArgs), vp]),
     'ag_gfront_bwd': (C.c_int, [C.POINTER(FrontBwdArgs), vp]),
+    'ag_gfront_stack_ok': (C.c_int, [C.c_int] * 5),
+    'ag_gfront_stack_ws_bytes': (i64, [C.c_int] * 4),
+    'ag_gfront_stack_fwd': (C.c_int, [C.POINTER(FrontStackArgs), vp]),
     'ag_build_zc': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'ag_critic_batch': (C.c_int, [vp, i64, vp, i64, C.c_int, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp,
                                   C.POINTER(i32), C.c_int, vp, vp, vp, C.c_int, vp, vp]),

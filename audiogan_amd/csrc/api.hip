@@ -26,7 +26,7 @@ extern "C" const char* ag_last_kernel(void) { return g_kernel; }
 // v12 - ag_last_kernel; v13 - the fronts' persistent launches take argument structs: ag_gfront_fwd, ag_gfront_bwd):
 // audiogan_amd/_lib.py refuses a library of another version, so Python that relies on a new mode can never drive an older build.
 // Still v13 with ag_ema_update / ag_ema_chunk: an ADDED entry point changes no existing call, and a library without it is
-// refused when _lib.py binds the missing symbol at import
+// refused when _lib.py binds the missing symbol at import (likewise the stacked front's ag_gfront_stack_ok / _ws_bytes / _fwd)
 extern "C" int ag_abi_version(void) { return 13; }
 extern "C" const char* ag_arch(void) { return "gfx950"; }
 extern "C" const char* ag_last_error(void) { return g_err; }

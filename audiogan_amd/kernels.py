@@ -1365,6 +1365,79 @@ def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=
     _front_launch('ag_gfront_fwd', a, x.device, int(lib.ag_gfront_persist_ws_bytes(B, S, fs)))
 
 
+# the stacked LSTM front (2 to 8 LSTMCell layers) in one persistent launch; off: one launch per operation and frame
+PERSIST_FRONT_STACK = [True]
+
+
+def gfront_stack_ok(B, S, fs, nl, dev):
+    return bool(PERSIST[0] and PERSIST_FRONT_STACK[0] and torch.device(dev).type == 'cuda'
+                and lib.ag_gfront_stack_ok(B, S, fs, nl, _n_cu(dev)))
+
+
+def _stack_tables(a, **tables):
+    """fills the per-layer pointer tables of a FrontStackArgs (entries past a list's end stay NULL)"""
+    for name, lst in tables.items():
+        arr = getattr(a, name)
+        for i, t in enumerate(lst):
+            arr[i] = _p(t)
+
+
+def gfront_stack_fwd_persist(gates, wx, w_in, whh, bias, wp, bp, hs, cs, x, xt=None):
+    """the frame loop of a STACKED LSTM front in ONE persistent launch (ag_gfront_stack_fwd, training).  Lists over the nl
+    layers: gates [T,B,4S] (gates[0] holds the z / c pre-activations incl. both biases and, like the others, receives the
+    activated gates), whh [4S,S], hs [T,B,S], cs [T+1,B,S]; for the layers from 1 on: w_in (W_ih_l [4S,S]) and bias
+    (b_ih_l + b_hh_l [4S]), nl - 1 entries each.  wx = W_ih_0[:, :fs] (any row pitch); x / xt as for gfront_fwd_persist"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S = S4 // 4
+    fs = wp.size(0)
+    assert len(whh) == len(hs) == len(cs) == nl and len(w_in) == len(bias) == nl - 1
+    rows = [(wp, 'wp', (fs, S)), (bp, 'bp', (fs,)), (xt, 'xt', (T, B, fs)), (x, 'x', (B, T * fs), _PITCHED),
+            (wx, 'wx', (4 * S, fs), _PITCHED)]
+    for l in range(nl):
+        rows += [(gates[l], 'gates[%d]' % l, (T, B, 4 * S)), (whh[l], 'whh[%d]' % l, (4 * S, S)),
+                 (hs[l], 'hs[%d]' % l, (T, B, S)), (cs[l], 'cs[%d]' % l, (T + 1, B, S))]
+    for l in range(nl - 1):
+        rows += [(w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)), (bias[l], 'bias[%d]' % (l + 1), (4 * S,))]
+    ld = _front_check(rows)
+    a = _lib.FrontStackArgs(gen=0, nl=nl, ldwx=ld['wx'], w_p=_p(wp), b_p=_p(bp), x=_p(x), ldx=ld['x'], xt=_p(xt),
+                            T=T, B=B, S=S, fs=fs)
+    _stack_tables(a, gates=gates, hs=hs, cs=cs, w_hh=whh, w_in=[wx] + list(w_in), bias=[None] + list(bias))
+    _front_launch('ag_gfront_stack_fwd', a, x.device, int(lib.ag_gfront_stack_ws_bytes(B, S, fs, nl)))
+
+
+def gfront_stack_gen_persist(pre, wx, w_in, whh, bias, wp, bp, ws, bs, u, x, s, first, t_run):
+    """the generation mode of the stacked front's launch (ag_gfront_stack_fwd, gen = 1): no history.  pre [T,B,4S] (layer 0's
+    z / c pre-activations) is only read; whh: nl tensors, w_in / bias: nl - 1 (layers 1 ..); the stop head (ws, bs), the
+    uniforms u and the outputs x, s, first, t_run as for gfront_gen_persist"""
+    nl = len(whh)
+    T, B, S4 = pre.shape
+    S = S4 // 4
+    fs = wp.size(0)
+    assert len(w_in) == len(bias) == nl - 1 and ws.numel() == S, (nl, len(w_in), len(bias), tuple(ws.shape))
+    rows = [(pre, 'pre', (T, B, 4 * S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)), (bs, 'bs', (1,)), (u, 'u', (T, B)),
+            (ws, 'ws', tuple(ws.shape)), (first, 'first', (B,), torch.int32), (t_run, 't_run', (1,), torch.int32),
+            (x, 'x', (B, T * fs), _PITCHED), (s, 's', (B, T), _PITCHED), (wx, 'wx', (4 * S, fs), _PITCHED)]
+    for l in range(nl):
+        rows.append((whh[l], 'whh[%d]' % l, (4 * S, S)))
+    for l in range(nl - 1):
+        rows += [(w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)), (bias[l], 'bias[%d]' % (l + 1), (4 * S,))]
+    ld = _front_check(rows)
+    a = _lib.FrontStackArgs(gen=1, nl=nl, ldwx=ld['wx'], w_p=_p(wp), b_p=_p(bp), w_s=_p(ws), b_s=_p(bs), u=_p(u), x=_p(x),
+                            ldx=ld['x'], s=_p(s), lds=ld['s'], first=_p(first), t_run=_p(t_run), T=T, B=B, S=S, fs=fs)
+    _stack_tables(a, gates=[pre], w_hh=whh, w_in=[wx] + list(w_in), bias=[None] + list(bias))
+    _front_launch('ag_gfront_stack_fwd', a, x.device, int(lib.ag_gfront_stack_ws_bytes(B, S, fs, nl)))
+
+
+def _work_gfront_stack(gates, wx, w_in, whh, *a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S, fs = S4 // 4, wx.size(1)
+    return None, T * 2.0 * B * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S), \
+        4.0 * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + fs)), 1
+
+
 def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):
     T, B, S3 = gates.shape
     S, fs = S3 // 3, wp.size(0)
@@ -1532,7 +1605,7 @@ def _work_seq_bwd_cell(gates, whh, *a_, **kw):
 for _n, _w in (('skinny_gemm', _work_skinny), ('lstm_step_fwd', _work_step),
                ('_lstm_seq_fwd_range', _work_seq_fwd), ('_lstm_seq_fwd_persist_call', _work_seq_fwd_persist),
                ('_lstm_seq_bwd_persist_call', _work_seq_bwd_persist), ('gfront_fwd_persist', _work_gfront), ('gfront_bwd_persist', _work_gfront_bwd), ('grufront_bwd_persist', _work_grufront_bwd),
-               ('grufront_fwd_persist', _work_grufront), ('_lstm_seq_bwd_prod', _work_seq_bwd_prod),
+               ('grufront_fwd_persist', _work_grufront), ('gfront_stack_fwd_persist', _work_gfront_stack), ('_lstm_seq_bwd_prod', _work_seq_bwd_prod),
                ('_lstm_seq_bwd_cell', _work_seq_bwd_cell), ('_lstm_seq_bwd_step', _work_seq_bwd_step)):
     _instrument(_n, _w)
 

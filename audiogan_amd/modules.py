@@ -173,8 +173,11 @@ class Generator(nn.Module):
         """does the frame loop of a forward at this batch size run as ONE persistent launch (all CUs, one such launch at
         a time per device)?  Callers that want to run two forwards side by side on two streams must not when it does."""
         from . import kernels as K
-        # (LSTM front: single layer only; the GRU front of GRUGenerator is always one layer - both take the same launch)
-        return self._num_layers == 1 and K.gfront_persist_ok(batch_size, self._state_size, self._frame_size, dev)
+        # (one layer: the launch the GRU front of GRUGenerator also takes; a stacked LSTM front has its own launch and its own
+        # predicate - never the one-layer predicate, which knows nothing of the layers' workgroups)
+        if self._num_layers > 1:
+            return K.gfront_stack_ok(batch_size, self._state_size, self._frame_size, self._num_layers, dev)
+        return K.gfront_persist_ok(batch_size, self._state_size, self._frame_size, dev)
 
     def prepare_weights(self):
         """materialise the weight-normed weights of every block NOW, on the current stream (no-op when the

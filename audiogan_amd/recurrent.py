@@ -343,13 +343,21 @@ class GFrontFn(torch.autograd.Function):
         _front_pre(zc, wz, lw[0][2], lw[0][3], gates[0], gru=False)
         fused0 = K.lstm_step_ok(B, S, x[:, :fs], wx)
         persist = nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev)
+        stack = nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_ok(B, S, fs, nl, dev)
         xt = None
-        if not persist:
+        if stack:
+            # the whole frame loop of ALL layers (every LSTMCell step + projection, fed back) in ONE launch; the history of
+            # every layer is written as the per-frame path below writes it, which is what the (per-frame) backward reads
+            xt = torch.empty(T, B, fs, device=dev)
+            K.gfront_stack_fwd_persist(gates, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
+                                       [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, hs, cs, x, xt)
+            persist = True      # (nothing below but the stop head is left to do)
+        elif not persist:
             for l in range(nl):
-                cs[l][0].zero_()                       # (the persistent launch writes c_0 = 0 itself)
+                cs[l][0].zero_()                       # (the persistent launches write c_0 = 0 themselves)
         h0 = None if persist else torch.zeros(B, S, device=dev)      # (only the per-frame path reads it)
         bsum = None if persist else [lw[l][2] + lw[l][3] for l in range(nl)]
-        if persist:
+        if persist and not stack:
             # the whole frame loop (LSTMCell step + projection, fed back) in ONE launch, weights resident in registers; the
             # frames are also written time-major (xt): what the weight gradient of W_ih[:, :fs] reads in backward
             xt = torch.empty(T, B, fs, device=dev)
@@ -633,7 +641,8 @@ def front_sample(front, zc, u):
     t when u[t,b] < sigmoid(s[b,t]) (the reference's Bernoulli draw, :450).  Returns (x [B, T*fs], s [B,T], first int64 [B])
     where first[b] = the frames clip b generates; only the first max(first) frames of x and s are meaningful.
 
-    Where the persistent launch fits (one layer, a supported (B, S, fs)): ONE ag_gfront_fwd launch (gen = 1), which draws the
+    Where a persistent launch fits (one layer: ag_gfront_fwd at a supported (B, S, fs); 2 to 8 LSTM layers:
+    ag_gfront_stack_fwd at a supported (B, S, fs, nl)): ONE launch (gen = 1), which draws the
     stops itself, keeps no history and leaves its frame loop one frame after every clip has stopped.  Otherwise the training
     front runs over all T frames under no_grad and the same rule is applied to its logits."""
     T, B, Fz = zc.shape
@@ -645,6 +654,19 @@ def front_sample(front, zc, u):
     w_ih, w_hh, b_ih, b_hh = [p_.w for p_ in prep[:4]]
     pw, pb, sw, sb = [p_.w for p_ in prep[4 * nl:4 * nl + 4]]
     wx, wz = w_ih[:, :fs], w_ih[:, fs:]
+    if nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_ok(B, S, fs, nl, dev):
+        # a stacked front: ONE ag_gfront_stack_fwd launch (gen = 1); the top layer's h feeds the projection and the stop head
+        lw = [[p_.w for p_ in prep[4 * l:4 * l + 4]] for l in range(nl)]
+        pre = torch.empty(T, B, 4 * S, device=dev)
+        _front_pre(zc, wz, b_ih, b_hh, pre, False)
+        x = _frames_buffer(front, B, T * fs, dev)
+        s = torch.empty(B, T, device=dev)
+        first = torch.empty(B, dtype=torch.int32, device=dev)
+        t_run = torch.empty(1, dtype=torch.int32, device=dev)
+        K.gfront_stack_gen_persist(pre, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
+                                   [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, sw.view(-1), sb, u.contiguous(),
+                                   x, s, first, t_run)
+        return x, s, first.long(), t_run
     if nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev):
         pre = torch.empty(T, B, (3 if gru else 4) * S, device=dev)
         _front_pre(zc, wz, b_ih, b_hh, pre, gru)

@@ -455,6 +455,51 @@ int ag_gfront_persist_ok(int B, int S, int fs, int n_cu);
 int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs);
 int ag_gfront_fwd(const ag_front_fwd_args* a, void* stream);
 
+/* The frame loop of a STACKED front (audiogan.py:382-385, :441-442: nl LSTMCell layers, 2 <= nl <= 8, under one projection
+ * and one stop head, both fed by the top layer's h) as ONE persistent launch (csrc/lstm_persist.hip), in the two modes of
+ * ag_gfront_fwd.  Frame t: layer 0 takes [x_{t-1}, zc_t] and its own h_{0,t-1}; layer l >= 1 takes h_{l-1,t} and its own
+ * h_{l,t-1}; x_t = tanh(h_{nl-1,t} W_p^T + b_p); (generation) s_t = h_{nl-1,t} . w_s + b_s, with the stop draws, the exit
+ * rule and the outputs s, first, t_run exactly as ag_gfront_fwd states them.  LSTMCell only.  fp32 MFMA; in bf16 mode
+ * (ag_set_precision) both operands of all three products are rounded in registers.
+ * Supported (ag_gfront_stack_ok): 2 <= nl <= 8; (S, fs) as for ag_gfront_persist_ok; 1 <= B <= 64 and
+ * nl * ceil(B/32) * S/8 <= min(n_cu, 256) workgroups (256 at the reference's B 32, S 1024, nl 2).  One layer is NOT this
+ * launch's business: ag_gfront_stack_ok answers 0 for nl = 1, which stays on ag_gfront_fwd.  `ws` =
+ * ag_gfront_stack_ws_bytes() bytes (one h exchange buffer more per layer; the same for every fs of a state size), used as
+ * for ag_lstm_seq_fwd_persist.
+ *
+ * Every tensor is fp32 and dense in the stated shape unless a pitch (in elements) is named; every w_hh, w_in, w_p and `ws`
+ * are 16-byte aligned, ldwx % 4 == 0.  The per-layer tables hold 8 entries: entries from nl on must be NULL, and so must a
+ * field that the mode (or the layer) does not use.  All of that, a wrong struct_bytes and T <= 0 are refused with AG_ERR_ARG
+ * before any HIP call; a shape outside the rule with AG_ERR_UNSUPPORTED. */
+typedef struct ag_front_stack_args {
+  int64_t struct_bytes; /* sizeof(ag_front_stack_args): a caller built against another layout is refused */
+  int32_t gen;          /* 0 training, 1 generation */
+  int32_t nl;           /* layers */
+  float* gates[8];      /* [T,B,4S] each.  [0], both modes: in = W_ih_0[:, fs:] zc_t + b_ih_0 + b_hh_0; training: out = activated
+                           gates; generation: only read.  [l >= 1], training only: out = activated gates (never read) */
+  float* hs[8];         /* training: [T,B,S] out, h_{l,t} */
+  float* cs[8];         /* training: [T+1,B,S] out (cs[l][0] is written 0 by the launch) */
+  const float* w_hh[8]; /* both: [4S,S] */
+  const float* w_in[8]; /* both.  [0]: W_ih_0[:, :fs], [4S,fs] with row pitch ldwx; [l >= 1]: W_ih_l [4S,S] */
+  const float* bias[8]; /* both.  [0]: NULL (its biases are inside gates[0]); [l >= 1]: b_ih_l + b_hh_l, [4S] */
+  const float* w_p;     /* both: [fs,S] */
+  const float* b_p;     /* both: [fs] */
+  float* x;             /* both: [B,T*fs] out, row pitch ldx (channel 0 of the conv trunk's slab, or dense) */
+  float* xt;            /* training, optional: [T,B,fs] out, the same frames time-major */
+  const float* w_s;     /* generation: [S], the materialised stop head */
+  const float* b_s;     /* generation: [1] */
+  const float* u;       /* generation: [T,B] uniforms */
+  float* s;             /* generation: [B,T] out, row pitch lds >= T: the stop logits of the frames run */
+  int32_t* first;       /* generation: [B] out, the frames clip b generates */
+  int32_t* t_run;       /* generation: [1] out, the frames run */
+  void* ws;             /* both: the workspace */
+  int64_t ldx, lds, ws_bytes;
+  int32_t ldwx, T, B, S, fs, n_cu;
+} ag_front_stack_args;
+int ag_gfront_stack_ok(int B, int S, int fs, int nl, int n_cu);
+int64_t ag_gfront_stack_ws_bytes(int B, int S, int fs, int nl);
+int ag_gfront_stack_fwd(const ag_front_stack_args* a, void* stream);
+
 /* The frame loop of the front's BACKWARD through time (audiogan.py:437-443 under .backward() :903) in one persistent
  * launch: per frame gx_t = (dx_ext[t] + dgates_{t+1} W_x)(1 - x_t^2), dh_t = dh_ext[t] + dgates_{t+1} W_hh + gx_t W_p,
  * dgates_t = cell backward (cell 1: torch.nn.GRUCell's).  Reads what the training forward saved; the outputs are what the
