@@ -57,6 +57,12 @@ class FrontBwdArgs(C.Structure):
         (n, i64) for n in ('ldx', 'lddx', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
 
 
+class FrontStackBwdArgs(C.Structure):
+    _fields_ = [('struct_bytes', i64), ('nl', i32), ('pad_', i32)] + [(n, vp * FRONT_MAX_LAYERS) for n in (
+        'ga', 'cs', 'w_hh', 'w_in', 'dgs')] + [(n, vp) for n in ('w_p', 'x', 'dh_ext', 'dx_ext', 'dxt', 'ws')] + [
+        (n, i64) for n in ('ldx', 'lddx', 'ws_bytes')] + [(n, i32) for n in ('ldwx', 'T', 'B', 'S', 'fs', 'n_cu')]
+
+
 class OptDesc(C.Structure):
     _fields_ = [('p', vp), ('grad', vp), ('s1', vp), ('s2', vp), ('n', i64)]
 
@@ -145,6 +151,9 @@ SIGNATURES = {
     'ag_gfront_stack_ok': (C.c_int, [C.c_int] * 5),
     'ag_gfront_stack_ws_bytes': (i64, [C.c_int] * 4),
     'ag_gfront_stack_fwd': (C.c_int, [C.POINTER(FrontStackArgs), vp]),
+    'ag_gfront_stack_bwd_ok': (C.c_int, [C.c_int] * 5),
+    'ag_gfront_stack_bwd_ws_bytes': (i64, [C.c_int] * 4),
+    'ag_gfront_stack_bwd': (C.c_int, [C.POINTER(FrontStackBwdArgs), vp]),
     'ag_build_zc': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'ag_critic_batch': (C.c_int, [vp, i64, vp, i64, C.c_int, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp,
                                   C.POINTER(i32), C.c_int, vp, vp, vp, C.c_int, vp, vp]),

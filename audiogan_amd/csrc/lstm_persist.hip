@@ -2118,3 +2118,390 @@ extern "C" int ag_gfront_bwd(const ag_front_bwd_args* a, void* stream) {
   AG_CHECK_LAUNCH(who);
   return AG_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Backward through time of a STACKED front (2 to 8 LSTMCell layers, L = nl - 1 the top one) as ONE persistent launch: the
+// one-layer launch above with a layer coordinate.  Per frame t = T-1 .. 0 (every term of frame T is zero):
+//   gx_t     = (dx_ext[t] + dg_{0,t+1} W_x) * (1 - x_t^2)                        -> dxt[t]
+//   dh_{L,t} = dh_ext[t] + dg_{L,t+1} W_hh_L + gx_t W_p
+//   dh_{l,t} = dg_{l,t+1} W_hh_l + dg_{l+1,t} W_ih_{l+1}                          l < L
+//   dg_{l,t} = cell backward(dh_{l,t}, dc_{l,t+1})                                -> dgs[l][t]; dc stays in a register
+// Workgroups per clip tile of 32: nl * S/16 h tiles (layer l, 16 columns of h_l) and ceil(fs/16) x tiles, the roles of the
+// one-layer kernel.  An h tile keeps its [4S x 16] panel of W_hh_l in registers; the top layer's also W_p's [fs x 16]
+// panel; an h tile of a layer l < L a second [4S x 16] panel, W_ih_{l+1}[:, cols].  At S = 1024 a panel is 256 KiB (128
+// registers per lane): beside the first one, 15 of a wave's 32 k units of the second (60 registers) stay in registers and
+// 17 lie in LDS (136 KiB beside the 16 KiB of `red`, of 160 KiB), laid out [wave][k unit][g][li][e]: lane (g, li) writes and reads
+// ITS four e values as one b128 at lane * 16 bytes of a 1 KiB unit - conflict free, and private to the lane that wrote it.
+// At S = 128 both panels are 16 registers.
+// Chain of a frame: the x tiles publish gx_t; the top h tiles publish dg_{L,t}; each lower layer waits for every dg_{l+1,t}
+// of its clip tile and publishes dg_{l,t}; then every tile forms its recurrent term of frame t-1 from its own layer's
+// dg_{l,t} (the x tiles from dg_{0,t}).  nl + 1 hand-offs per frame.  Every frame has its own slot in dgs[l] / dxt, written
+// once and never again, so no reader can meet a later frame's value: no parity, no second buffer; flags count frames.
+// ------------------------------------------------------------------------------------------
+struct FrontStackBwdP {
+  const float* ga[FRONT_MAX_LAYERS];     // [T,B,4S] activated gates per layer
+  const float* cs[FRONT_MAX_LAYERS];     // [T+1,B,S]
+  const float* whh[FRONT_MAX_LAYERS];    // [4S,S]
+  const float* win[FRONT_MAX_LAYERS];    // [0]: W_ih_0[:, :fs] with pitch ldwx; [l>=1]: W_ih_l [4S,S]
+  float* dgs[FRONT_MAX_LAYERS];          // [T,B,4S] out (and exchange)
+  const float* wp;     // [fs,S]
+  const float* x;      // [B,T*fs], row pitch ldx
+  const float* dh_ext; // [T,B,S] or NULL: lands on the top layer only
+  const float* dx_ext; // [B,T*fs], row pitch lddx, or NULL
+  float* dxt;          // [T,B,fs] out (and exchange)
+  int64_t ldx, lddx;
+  PersistCtl ctl;
+  int T, B, ldwx, fs, nl;
+};
+
+// 16-k units per wave of a lower layer's second panel that lie in LDS (1 KiB each; 17 * 8 waves + `red` = 152 of 160 KiB)
+#define FRONT_STACK_BWD_LDS_UNITS(NU) ((NU) > 16 ? 17 : 0)
+
+// One body per role (ROLE 0: x tile, 1: h tile of the top layer, 2: h tile of a lower layer), so that the registers of a
+// role hold only what that role keeps: the kernel branches to one of them once.
+template <int S, int FS, bool RB, int ROLE>
+__device__ __forceinline__ void front_stack_bwd_body(const FrontStackBwdP& p, float* red, float* w2l, int* s_dead, int bt, int ct, int l) {
+  constexpr bool isx = ROLE == 0, top = ROLE == 1, low = ROLE == 2;
+  constexpr int K4 = 4 * S, NU = K4 / 128;                  // 16-k units of a big product per wave
+  constexpr int NHT = S / 16;
+  constexpr int NP = FS >= 128 ? FS / 128 : 1;              // 16-k units of the projection product per wave
+  constexpr int NL2 = FRONT_STACK_BWD_LDS_UNITS(NU);        // units of the second panel kept in LDS, per wave
+  constexpr int NR2 = NU - NL2;                             // ... and in registers
+  constexpr int NW2 = low ? NR2 : NP;
+  const int T = p.T, B = p.B, fs = p.fs, nl = p.nl;
+  const int NXT = (fs + 15) >> 4, NT = nl * NHT + NXT;      // x tiles / all tiles per clip tile
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int li = lane & 15, g = lane >> 4;
+  const int m0 = bt * 32;
+  const int n0 = (isx ? ct - nl * NHT : ct - l * NHT) * 16; // first column inside W_hh_l / W_x
+  const int64_t BG = (int64_t)B * K4, BH = (int64_t)B * S, BX = (int64_t)B * fs;
+
+  // The panels are fetched once, with buffer loads: element [16 * unit + 4g + e][n0 + li] of a matrix of row pitch ldw is
+  // at scalar offset (unit * 16 * ldw) + lane offset ((4g + e) * ldw + n0 + li) - four lane offsets serve a whole panel
+  const int widu = __builtin_amdgcn_readfirstlane(wid);
+  auto panel = [&](__amdgpu_buffer_rsrc_t r, int ldw, int unit, int e) {
+    return ag_rbf_if(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (unsigned)(((4 * g + e) * ldw + n0 + li) * 4),
+                                                                           (unsigned)(unit * 16 * ldw * 4), 0)), RB);
+  };
+  // resident panel: wreg[u][e] = W[(wid*NU + u)*16 + 4g + e][n0 + li]
+  float wreg[NU][4];
+  {
+    const float* W = isx ? p.win[0] : p.whh[l];
+    const int ldw = isx ? p.ldwx : S;
+    const bool wv = !isx || n0 + li < fs;                   // (x tiles: columns at or past fs are the z/c weights - zeros instead)
+    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, (int)(((int64_t)(K4 - 1) * ldw + (isx ? fs : S)) * 4), 0x00020000);
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wreg[u][e] = wv ? panel(wr, ldw, widu * NU + u, e) : 0.f;
+  }
+  // second panel.  Top layer: w2[u][e] = W_p[(wid*NP + u)*16 + 4g + e][n0 + li], u < NP (rows at or past fs: zeros).
+  // Lower layers: W_ih_{l+1}[(wid*NU + u)*16 + 4g + e][n0 + li]: units below NR2 in w2, the others in LDS.
+  const bool pw_on = top && (wid * NP * 16 < fs);
+  float w2[NW2][4];
+  bool pkv[NP];
+  (void)w2;
+#pragma unroll
+  for (int u = 0; u < NP; ++u) pkv[u] = pw_on && (wid * NP + u) * 16 + 4 * g < fs;
+  if constexpr (low) {
+    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.win[l + 1]), 0, K4 * S * 4, 0x00020000);
+#pragma unroll
+    for (int u = 0; u < NR2; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w2[u][e] = panel(wr, S, widu * NU + u, e);
+    if constexpr (NL2 > 0) {
+#pragma unroll
+      for (int u = 0; u < NL2; ++u) {
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = panel(wr, S, widu * NU + NR2 + u, e);
+        *reinterpret_cast<f32x4*>(&w2l[(wid * NL2 + u) * 256 + lane * 4]) = v;
+      }
+    }
+  } else if constexpr (top) {
+    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, fs * S * 4, 0x00020000);
+#pragma unroll
+    for (int u = 0; u < NP; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w2[u][e] = pkv[u] ? panel(wr, S, widu * NP + u, e) : 0.f;
+  }
+  __syncthreads();
+
+  unsigned* flags_t = p.ctl.hdr + PS_FLAG_OFF + bt * NT;    // [layer][h tile], then the x tiles
+  unsigned* flags_own = flags_t + l * NHT;                  // the dgates this workgroup's recurrent term reads
+  unsigned* flags_up = flags_t + (l + 1) * NHT;             // lower layers: the layer above
+  unsigned* flags_x = flags_t + nl * NHT;
+  unsigned* my_flag = flags_t + ct;
+  const float* ga = p.ga[l];
+  const float* c_all = p.cs[l];
+  float* dg_own = p.dgs[l];
+  float* dg_up = p.dgs[low ? l + 1 : l];
+  // epilogue role: thread <-> (clip row, column of the tile)
+  const int erow = tid >> 4, ecol = tid & 15;
+  const int em = m0 + erow;
+  const bool epi = em < B && (!isx || n0 + ecol < fs);      // (x tiles: columns at or past fs do not exist)
+  const unsigned og4 = (unsigned)(((int64_t)em * K4 + n0 + ecol) * 4);      // this thread's byte offsets inside a frame of
+  const unsigned oc4 = (unsigned)(((int64_t)em * S + n0 + ecol) * 4);       // gates / dgates, and of c / dh_ext
+  // A operand rows of this lane for the two 16-clip halves (clamped: rows past the batch feed only their own, unwritten outputs)
+  const int ar0 = min(m0 + li, B - 1), ar1 = min(m0 + 16 + li, B - 1);
+  const unsigned o0 = (unsigned)(((int64_t)ar0 * K4 + wid * NU * 16 + 4 * g) * 4);
+  const unsigned o1 = (unsigned)(((int64_t)ar1 * K4 + wid * NU * 16 + 4 * g) * 4);
+  constexpr int UB = NU < 4 ? NU : 4;                       // units loaded per batch (a unit's offset rides in the scalar offset:
+                                                            // added to the lane offset it would cost a register per load)
+  float carry = 0.f, dcn = 0.f;
+  bool alive = true;
+
+  for (int t = T - 1; t >= 0; --t) {
+    const unsigned seq = (unsigned)(T - t);
+    if constexpr (isx) {
+      if (epi) {
+        const float dx = (p.dx_ext ? p.dx_ext[(int64_t)em * p.lddx + (int64_t)t * fs + n0 + ecol] : 0.f) + carry;
+        const float xv = p.x[(int64_t)em * p.ldx + (int64_t)t * fs + n0 + ecol];
+        float gx = dx * (1.f - xv * xv);
+        if (*s_dead) gx = __builtin_nanf("");
+        __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(p.dxt + (int64_t)t * BX, 0, (int)(BX * 4), 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gx), orr, (unsigned)(((int64_t)em * fs + n0 + ecol) * 4), 0, 16);
+      }
+    } else {
+      float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, cp = 0.f, cn = 0.f, ext = 0.f;
+      if (epi) {
+        // (what the forward saved: plain cached loads, nobody writes these during the launch)
+        __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ga) + (int64_t)t * BG, 0, (int)(BG * 4), 0x00020000);
+        __amdgpu_buffer_rsrc_t cr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c_all) + (int64_t)t * BH, 0, (int)(2 * BH * 4), 0x00020000);
+        ig = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(gr, og4, 0, 0));
+        fg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(gr, og4 + (unsigned)(S * 4), 0, 0));
+        gg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(gr, og4 + (unsigned)(2 * S * 4), 0, 0));
+        og = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(gr, og4 + (unsigned)(3 * S * 4), 0, 0));
+        cp = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cr, oc4, 0, 0));                        // c_{t-1}
+        cn = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cr, oc4, (unsigned)(BH * 4), 0));       // c_t
+        if (top && p.dh_ext) {
+          __amdgpu_buffer_rsrc_t er = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dh_ext) + (int64_t)t * BH, 0, (int)(BH * 4), 0x00020000);
+          ext = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(er, oc4, 0, 0));
+        }
+      }
+      if (wid == 0 && alive) {
+        alive = top ? ps_wait_flags<true>(p.ctl, flags_x, NXT, seq, lane) : ps_wait_flags(p.ctl, flags_up, NHT, seq, lane);
+        if (!alive) *s_dead = 1;
+      }
+      __syncthreads();
+      f32x4 pa[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+      if constexpr (top) {
+        // gx_t [32 clips, fs] x W_p panel
+        if (pw_on) {
+          __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dxt) + (int64_t)t * BX, 0, (int)(BX * 4), 0x00020000);
+          u32x4 a[2][NP];
+#pragma unroll
+          for (int u = 0; u < NP; ++u) {
+            const unsigned ko = (unsigned)(((wid * NP + u) * 16 + 4 * g) * 4);
+            a[0][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar0 * fs * 4) + ko, 0, 16);
+            a[1][u] = __builtin_amdgcn_raw_buffer_load_b128(xr, (unsigned)(ar1 * fs * 4) + ko, 0, 16);
+          }
+          if (fs < FS) {     // k at or past fs: the load ran into the next clip's row (or past the buffer: zeros)
+#pragma unroll
+            for (int u = 0; u < NP; ++u)
+              if (!pkv[u]) a[0][u] = a[1][u] = u32x4{0u, 0u, 0u, 0u};
+          }
+#pragma unroll
+          for (int u = 0; u < NP; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+              for (int r = 0; r < 2; ++r)
+                pa[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(ag_rbf_if(__uint_as_float(a[r][u][e]), RB), w2[u][e], pa[r], 0, 0, 0);
+        }
+      } else {
+        // dg_{l+1,t} [32 clips, 4S] x W_ih_{l+1} panel: the register part, then the LDS part
+        __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(dg_up + (int64_t)t * BG, 0, (int)(BG * 4), 0x00020000);
+#pragma unroll
+        for (int ub = 0; ub < NU; ub += UB) {
+          u32x4 a[2][UB];
+#pragma unroll
+          for (int i = 0; i < UB; ++i) {
+            a[0][i] = __builtin_amdgcn_raw_buffer_load_b128(gr, o0, (unsigned)((ub + i) * 64), 16);
+            a[1][i] = __builtin_amdgcn_raw_buffer_load_b128(gr, o1, (unsigned)((ub + i) * 64), 16);
+          }
+#pragma unroll
+          for (int i = 0; i < UB; ++i) {
+            f32x4 wv;
+            if (ub + i < NR2) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) wv[e] = w2[ub + i < NW2 ? ub + i : 0][e];
+            } else {
+              wv = *reinterpret_cast<const f32x4*>(&w2l[(wid * NL2 + (ub + i - NR2)) * 256 + lane * 4]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+              for (int r = 0; r < 2; ++r)
+                pa[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(ag_rbf_if(__uint_as_float(a[r][i][e]), RB), wv[e], pa[r], 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wid * 512 + (16 * r + 4 * g + e) * 16 + li] = pa[r][e];
+      __syncthreads();
+      if (epi) {
+        float dhv = ext + carry;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) dhv += red[w * 512 + tid];
+        __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(dg_own + (int64_t)t * BG, 0, (int)(BG * 4), 0x00020000);
+        const float tc = tanhf(cn);
+        const float dc = dcn + dhv * og * (1.f - tc * tc);
+        float d0 = dc * gg * ig * (1.f - ig);
+        float d1 = dc * cp * fg * (1.f - fg);
+        float d2 = dc * ig * (1.f - gg * gg);
+        float d3 = dhv * tc * og * (1.f - og);
+        dcn = dc * fg;
+        if (*s_dead) { d0 = d1 = d2 = d3 = dcn = __builtin_nanf(""); }   // a wait timed out: poison instead of garbage
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d0), orr, og4, 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d1), orr, og4 + (unsigned)(S * 4), 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d2), orr, og4 + (unsigned)(2 * S * 4), 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d3), orr, og4 + (unsigned)(3 * S * 4), 0, 16);
+      }
+    }
+    if (t == 0 && !isx && l == 0) break;                      // dg_{0,0} has no reader inside the launch
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // EVERY storing wave drains its write-through stores
+    __syncthreads();
+    if (tid == 0 && (int)blockIdx.x != p.ctl.mute)
+      __hip_atomic_store(my_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) break;
+    // ---- the recurrent term of frame t-1: dg_{l,t} [32 clips, 4S] x the register panel
+    if (wid == 0 && alive) {
+      alive = ps_wait_flags(p.ctl, flags_own, NHT, seq, lane);
+      if (!alive) *s_dead = 1;
+    }
+    __syncthreads();
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    {
+      __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(dg_own + (int64_t)t * BG, 0, (int)(BG * 4), 0x00020000);
+#pragma unroll
+      for (int ub = 0; ub < NU; ub += UB) {
+        u32x4 a[2][UB];
+#pragma unroll
+        for (int i = 0; i < UB; ++i) {
+          a[0][i] = __builtin_amdgcn_raw_buffer_load_b128(gr, o0, (unsigned)((ub + i) * 64), 16);
+          a[1][i] = __builtin_amdgcn_raw_buffer_load_b128(gr, o1, (unsigned)((ub + i) * 64), 16);
+        }
+#pragma unroll
+        for (int i = 0; i < UB; ++i)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+              acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(ag_rbf_if(__uint_as_float(a[r][i][e]), RB), wreg[ub + i][e], acc[r], 0, 0, 0);
+      }
+    }
+    // C layout of a 16x16 tile: col = lane & 15, row = 4 * (lane >> 4) + e
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[wid * 512 + (16 * r + 4 * g + e) * 16 + li] = acc[r][e];
+    __syncthreads();
+    carry = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) carry += red[w * 512 + tid];
+    __syncthreads();                                          // red is written again in the next frame
+  }
+}
+
+template <int S, int FS, bool RB>
+__global__ __launch_bounds__(512) void gfront_stack_bwd_kernel(const FrontStackBwdP p) {
+  constexpr int NHT = S / 16, NU = 4 * S / 128, NL2 = FRONT_STACK_BWD_LDS_UNITS(NU);
+  static_assert(NU * 128 == 4 * S && FS % 16 == 0 && FS / 16 <= 64 && S % 16 == 0, "shape");
+  __shared__ float red[8 * 512];
+  __shared__ __attribute__((aligned(16))) float w2l[NL2 > 0 ? 8 * NL2 * 256 : 4];      // [wave][k unit][g][li][e]
+  __shared__ int s_dead;
+  if (threadIdx.x == 0) s_dead = 0;
+  __syncthreads();
+  const int NT = p.nl * NHT + ((p.fs + 15) >> 4);           // tiles per clip tile
+  const int bt = blockIdx.x / NT, ct = blockIdx.x % NT;
+  if (ct >= p.nl * NHT) {
+    front_stack_bwd_body<S, FS, RB, 0>(p, red, w2l, &s_dead, bt, ct, 0);      // (x tiles read layer 0's dgates)
+  } else {
+    const int l = ct / NHT;
+    if (l == p.nl - 1) front_stack_bwd_body<S, FS, RB, 1>(p, red, w2l, &s_dead, bt, ct, l);
+    else front_stack_bwd_body<S, FS, RB, 2>(p, red, w2l, &s_dead, bt, ct, l);
+  }
+}
+
+// workgroups of the stacked backward: per clip tile nl * S/16 h tiles and ceil(fs/16) x tiles
+static int64_t front_stack_bwd_grid(int B, int S, int fs, int nl) { return (int64_t)ag_cdiv(B, 32) * ((int64_t)nl * (S / 16) + ag_cdiv(fs, 16)); }
+
+static bool front_stack_bwd_shape_ok(int B, int S, int fs, int nl, int n_cu) {
+  if (nl < 2 || nl > FRONT_MAX_LAYERS) return false;
+  if (!front_fs_ok(S, fs)) return false;
+  if (B < 1) return false;
+  if (n_cu > 256) n_cu = 256;
+  const int64_t grid = front_stack_bwd_grid(B, S, fs, nl);
+  return grid <= n_cu && grid <= (PS_HDR_BYTES / 4 - PS_FLAG_OFF);
+}
+
+extern "C" int ag_gfront_stack_bwd_ok(int B, int S, int fs, int nl, int n_cu) { return front_stack_bwd_shape_ok(B, S, fs, nl, n_cu) ? 1 : 0; }
+
+extern "C" int64_t ag_gfront_stack_bwd_ws_bytes(int B, int S, int fs, int nl) {
+  (void)B; (void)S; (void)fs; (void)nl;      // (dgs / dxt are the exchange buffers: the sticky word and the header only)
+  return PS_STICKY_BYTES + PS_HDR_BYTES;
+}
+
+template <int S, int FS, bool RB>
+static void front_stack_bwd_launch(const FrontStackBwdP& p, int grid, hipStream_t st) {
+  static const AgKernelName name("gfront_stack_bwd_kernel", {S, FS, RB ? 1 : 0});
+  ag_note_kernel(name.s);
+  hipLaunchKernelGGL((gfront_stack_bwd_kernel<S, FS, RB>), dim3(grid), dim3(512), 0, st, p);
+}
+
+// The backward through time of a front with 2 to 8 LSTMCell layers in ONE launch.  Tensor contracts:
+// ag_front_stack_bwd_args (include/audiogan_hip.h).  Shapes: ag_gfront_stack_bwd_ok.
+extern "C" int ag_gfront_stack_bwd(const ag_front_stack_bwd_args* a, void* stream) {
+  static const char* const who = "ag_gfront_stack_bwd";
+  AG_REQUIRE(a && a->struct_bytes == (int64_t)sizeof(*a), "%s: struct_bytes = %lld, but ag_front_stack_bwd_args has %zu bytes in this library",
+             who, a ? (long long)a->struct_bytes : -1LL, sizeof(*a));
+  AG_REQUIRE(a->nl >= 1 && a->nl <= FRONT_MAX_LAYERS, "%s: nl = %d, the per-layer tables hold 1 to %d layers", who, a->nl, FRONT_MAX_LAYERS);
+  const int nl = a->nl;
+  static const char* const idx[FRONT_MAX_LAYERS] = {"[0]", "[1]", "[2]", "[3]", "[4]", "[5]", "[6]", "[7]"};
+  for (int l = 0; l < FRONT_MAX_LAYERS; ++l) {
+    const bool in = l < nl;
+    const struct { const char* name; const void* p; } f[] = {
+        {"ga", a->ga[l]}, {"cs", a->cs[l]}, {"w_hh", a->w_hh[l]}, {"w_in", a->w_in[l]}, {"dgs", a->dgs[l]}};
+    for (const auto& e : f)
+      AG_REQUIRE((e.p != nullptr) == in, "%s: %s%s %s", who, e.name, idx[l], in ? "is NULL" : "lies past nl and must be NULL");
+  }
+  const FrontField fields[] = {
+      {"w_p", a->w_p, true}, {"x", a->x, true}, {"dh_ext", a->dh_ext, a->dh_ext != nullptr}, {"dx_ext", a->dx_ext, a->dx_ext != nullptr},      // (optional)
+      {"dxt", a->dxt, true}, {"ws", a->ws, true}};
+  if (int rc = front_fields_ok(who, fields)) return rc;
+  const int T = a->T, B = a->B, S = a->S, fs = a->fs;
+  AG_REQUIRE(T > 0, "%s: T must be positive", who);
+  AG_REQUIRE(a->ldx >= (int64_t)T * fs, "%s: x row pitch smaller than a row", who);
+  AG_REQUIRE(!a->dx_ext || a->lddx >= (int64_t)T * fs, "%s: dx_ext row pitch smaller than a row", who);
+  AG_REQUIRE(a->ldwx >= fs, "%s: w_in[0] row pitch smaller than a row", who);
+  if (!front_stack_bwd_shape_ok(B, S, fs, nl, a->n_cu)) {
+    ag_set_error("%s: shape B=%d S=%d fs=%d nl=%d is not supported on %d CUs", who, B, S, fs, nl, a->n_cu);
+    return AG_ERR_UNSUPPORTED;
+  }
+  AG_REQUIRE((int64_t)B * 4 * S * 4 < ((int64_t)1 << 31), "%s: frame slab too large", who);
+  uintptr_t al = (uintptr_t)a->dxt;
+  for (int l = 0; l < nl; ++l) al |= (uintptr_t)a->dgs[l];
+  AG_REQUIRE((al & 15) == 0, "%s: outputs must be 16-byte aligned", who);
+  hipStream_t st = (hipStream_t)stream;
+  FrontStackBwdP p;
+  if (int rc = persist_begin(who, a->ws, a->ws_bytes, ag_gfront_stack_bwd_ws_bytes(B, S, fs, nl), st, &p.ctl)) return rc;
+  for (int l = 0; l < FRONT_MAX_LAYERS; ++l) {
+    p.ga[l] = a->ga[l]; p.cs[l] = a->cs[l]; p.whh[l] = a->w_hh[l]; p.win[l] = a->w_in[l]; p.dgs[l] = a->dgs[l];
+  }
+  p.wp = a->w_p; p.x = a->x; p.ldx = a->ldx; p.dh_ext = a->dh_ext; p.dx_ext = a->dx_ext; p.lddx = a->lddx; p.dxt = a->dxt;
+  p.T = T; p.B = B; p.ldwx = a->ldwx; p.fs = fs; p.nl = nl;
+  const bool rb = ag_precision() == AG_PREC_BF16;
+  const int grid = (int)front_stack_bwd_grid(B, S, fs, nl);
+  if (S == 1024) {
+    if (rb) front_stack_bwd_launch<1024, 256, true>(p, grid, st);
+    else front_stack_bwd_launch<1024, 256, false>(p, grid, st);
+  } else {
+    if (rb) front_stack_bwd_launch<128, 64, true>(p, grid, st);
+    else front_stack_bwd_launch<128, 64, false>(p, grid, st);
+  }
+  AG_CHECK_LAUNCH(who);
+  return AG_OK;
+}

@@ -1438,6 +1438,49 @@ def _work_gfront_stack(gates, wx, w_in, whh, *a_, **kw):
         4.0 * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + fs)), 1
 
 
+# the stacked front's backward through time in one persistent launch; off: one launch per operation and frame
+PERSIST_FRONT_STACK_BWD = [True]
+
+
+def gfront_stack_bwd_ok(B, S, fs, nl, dev):
+    """(PERSIST_FRONT_BWD: the multi-GPU rule of the one-layer backward holds for this launch too)"""
+    return bool(PERSIST[0] and PERSIST_FRONT_STACK[0] and PERSIST_FRONT_STACK_BWD[0] and PERSIST_FRONT_BWD[0]
+                and torch.device(dev).type == 'cuda' and lib.ag_gfront_stack_bwd_ok(B, S, fs, nl, _n_cu(dev)))
+
+
+def gfront_stack_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, dgs, dxt):
+    """the backward through time of a STACKED LSTM front in ONE persistent launch (ag_gfront_stack_bwd).  Lists over the nl
+    layers: gates [T,B,4S] (activated), cs [T+1,B,S], whh [4S,S], dgs [T,B,4S] (out); w_in: W_ih_l [4S,S] of the layers from
+    1 on, nl - 1 entries; wx = W_ih_0[:, :fs] (any row pitch).  dh_ext / dx_ext / x / dxt as for gfront_bwd_persist: the
+    external gradients may be None, dh_ext is the TOP layer's"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S = S4 // 4
+    fs = wp.size(0)
+    assert len(cs) == len(whh) == len(dgs) == nl and len(w_in) == nl - 1
+    rows = [(wp, 'wp', (fs, S)), (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)), (x, 'x', (B, T * fs), _PITCHED),
+            (dx_ext, 'dx_ext', (B, T * fs), _PITCHED), (wx, 'wx', (4 * S, fs), _PITCHED)]
+    for l in range(nl):
+        rows += [(gates[l], 'gates[%d]' % l, (T, B, 4 * S)), (cs[l], 'cs[%d]' % l, (T + 1, B, S)),
+                 (whh[l], 'whh[%d]' % l, (4 * S, S)), (dgs[l], 'dgs[%d]' % l, (T, B, 4 * S))]
+    for l in range(nl - 1):
+        rows.append((w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)))
+    ld = _front_check(rows)
+    a = _lib.FrontStackBwdArgs(nl=nl, w_p=_p(wp), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext), dx_ext=_p(dx_ext),
+                               lddx=ld['dx_ext'], ldwx=ld['wx'], dxt=_p(dxt), T=T, B=B, S=S, fs=fs)
+    _stack_tables(a, ga=gates, cs=cs, w_hh=whh, w_in=[wx] + list(w_in), dgs=dgs)
+    _front_launch('ag_gfront_stack_bwd', a, x.device, int(lib.ag_gfront_stack_bwd_ws_bytes(B, S, fs, nl)))
+
+
+def _work_gfront_stack_bwd(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, *a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S, fs = S4 // 4, wp.size(0)
+    return None, 2.0 * B * ((T - 1) * S4 * (nl * S + fs) + T * ((nl - 1) * S4 * S + fs * S)), \
+        4.0 * (S4 * (nl * S + fs) + (nl - 1) * S4 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + S + 3 * fs)), 1
+
+
 def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):
     T, B, S3 = gates.shape
     S, fs = S3 // 3, wp.size(0)
@@ -1605,7 +1648,8 @@ def _work_seq_bwd_cell(gates, whh, *a_, **kw):
 for _n, _w in (('skinny_gemm', _work_skinny), ('lstm_step_fwd', _work_step),
                ('_lstm_seq_fwd_range', _work_seq_fwd), ('_lstm_seq_fwd_persist_call', _work_seq_fwd_persist),
                ('_lstm_seq_bwd_persist_call', _work_seq_bwd_persist), ('gfront_fwd_persist', _work_gfront), ('gfront_bwd_persist', _work_gfront_bwd), ('grufront_bwd_persist', _work_grufront_bwd),
-               ('grufront_fwd_persist', _work_grufront), ('gfront_stack_fwd_persist', _work_gfront_stack), ('_lstm_seq_bwd_prod', _work_seq_bwd_prod),
+               ('grufront_fwd_persist', _work_grufront), ('gfront_stack_fwd_persist', _work_gfront_stack),
+               ('gfront_stack_bwd_persist', _work_gfront_stack_bwd),('_lstm_seq_bwd_prod', _work_seq_bwd_prod),
                ('_lstm_seq_bwd_cell', _work_seq_bwd_cell), ('_lstm_seq_bwd_step', _work_seq_bwd_step)):
     _instrument(_n, _w)
 

@@ -347,7 +347,8 @@ class GFrontFn(torch.autograd.Function):
         xt = None
         if stack:
             # the whole frame loop of ALL layers (every LSTMCell step + projection, fed back) in ONE launch; the history of
-            # every layer is written as the per-frame path below writes it, which is what the (per-frame) backward reads
+            # every layer is written as the per-frame path below writes it, which is what the backward reads: one launch as
+            # well where K.gfront_stack_bwd_ok holds (ag_gfront_stack_bwd), the per-frame chain otherwise
             xt = torch.empty(T, B, fs, device=dev)
             K.gfront_stack_fwd_persist(gates, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
                                        [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, hs, cs, x, xt)
@@ -483,9 +484,18 @@ class GFrontFn(torch.autograd.Function):
             (wx.stride(1) == 1 and K.gfront_bwd_persist_ok(B, S, fs, dev))
             or ((S + fs) % 4 == 0 and K.lstm_front_bwd_ok(B, S, fs, x[:, :fs], x[:, :fs])
                 and K.skinny_ok(gates[0][0], lw[0][1], False)))
+        stack = nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_bwd_ok(B, S, fs, nl, dev)
         if fused:
             dgs, dxt = GFrontFn._bwd_frames_fused(T, B, fs, S, x, dx, ds, gates[0], cs[0], lw[0][1], wx, pw, sw,
                                                   hs[0], dws, nl)
+        elif stack:
+            # the whole loop of ALL layers in ONE launch (ag_gfront_stack_bwd); the stop head's gradient lands on the top layer
+            ds_tb = _stop_head_grads(ds, hs[-1].view(T * B, S), dws, 4 * nl + 2, defer=False) if ds is not None else None
+            dh_ext, dx_ext = _ext_grads(ds_tb, sw, dx, T, B, S)
+            dgs = [torch.empty(T, B, 4 * S, device=dev) for _ in range(nl)]
+            dxt = torch.empty(T, B, fs, device=dev)
+            K.gfront_stack_bwd_persist(gates, cs, x, dh_ext, dx_ext, [lw[l][1] for l in range(nl)],
+                                       [lw[l][0] for l in range(1, nl)], wx, pw, dgs, dxt)
         else:
             dgs, dxt = GFrontFn._bwd_frames(T, B, fs, S, nl, x, dx, ds, gates, cs, lw, wx, pw, sw, hs, dws)
         # parameter gradients, one GEMM per tensor over all frames

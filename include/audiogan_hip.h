@@ -531,6 +531,45 @@ typedef struct ag_front_bwd_args {
 int ag_gfront_bwd_persist_ok(int B, int S, int fs, int n_cu);
 int ag_gfront_bwd(const ag_front_bwd_args* a, void* stream);
 
+/* The BACKWARD through time of a STACKED front (2 <= nl <= 8 LSTMCell layers, L = nl - 1 the top one) in one persistent
+ * launch (csrc/lstm_persist.hip).  Per frame t = T-1 .. 0, every term of frame T being zero:
+ *   gx_t     = (dx_ext[t] + dg_{0,t+1} W_x)(1 - x_t^2)                     -> dxt[t]
+ *   dh_{L,t} = dh_ext[t] + dg_{L,t+1} W_hh_L + gx_t W_p                    (the stop head's gradient lands on the top layer only)
+ *   dh_{l,t} = dg_{l,t+1} W_hh_l + dg_{l+1,t} W_ih_{l+1}                   l < L
+ *   dg_{l,t} = LSTM cell backward(dh_{l,t}, dc_{l,t+1})                    -> dgs[l][t]
+ * Reads what ag_gfront_stack_fwd (or the per-frame forward) saved; the outputs are what the weight-gradient GEMMs over all
+ * frames read.  fp32 MFMA; in bf16 mode (ag_set_precision) both operands of all four products are rounded in registers.
+ * Supported (ag_gfront_stack_bwd_ok): 2 <= nl <= 8 (0 for nl = 1, which stays on ag_gfront_bwd); (S, fs) as for
+ * ag_gfront_persist_ok; B >= 1 and a grid of ceil(B/32) * (nl * S/16 + ceil(fs/16)) workgroups <= min(n_cu, 256) (141 at the
+ * reference's nl 2, B 32, S 1024, fs 200).  `ws` = ag_gfront_stack_bwd_ws_bytes() bytes: the sticky word + 8 KiB header
+ * (dgs / dxt are the exchange buffers).
+ *
+ * Every tensor is fp32 and dense in the stated shape unless a pitch (in elements) is named; every dgs[l], dxt and `ws` are
+ * 16-byte aligned.  The per-layer tables hold 8 entries: every entry below nl must be set, entries from nl on must be
+ * NULL.  All of that, a wrong struct_bytes, T <= 0 and a pitch smaller than a row are refused with AG_ERR_ARG before any HIP
+ * call; a shape outside the rule with AG_ERR_UNSUPPORTED. */
+typedef struct ag_front_stack_bwd_args {
+  int64_t struct_bytes; /* sizeof(ag_front_stack_bwd_args) */
+  int32_t nl;           /* layers */
+  int32_t pad_;
+  const float* ga[8];   /* [T,B,4S] each: the activated gates (i, f, g, o) of layer l */
+  const float* cs[8];   /* [T+1,B,S] each: cs[l][t] = c_{l,t-1}, cs[l][0] = 0 */
+  const float* w_hh[8]; /* [4S,S] each */
+  const float* w_in[8]; /* [0]: W_ih_0[:, :fs], [4S,fs] with row pitch ldwx; [l >= 1]: W_ih_l [4S,S] */
+  float* dgs[8];        /* [T,B,4S] each, out: d gate pre-activations of layer l */
+  const float* w_p;     /* [fs,S] */
+  const float* x;       /* [B,T*fs] the front's output (after tanh), row pitch ldx */
+  const float* dh_ext;  /* optional (NULL = zero): [T,B,S] = dL/dh_{L,t}, the stop head's; read only */
+  const float* dx_ext;  /* optional (NULL = zero): [B,T*fs] = dL/dx_t, the conv trunk's, row pitch lddx; read only */
+  float* dxt;           /* [T,B,fs] out, d pre-tanh of the projection */
+  void* ws;
+  int64_t ldx, lddx, ws_bytes;
+  int32_t ldwx, T, B, S, fs, n_cu;
+} ag_front_stack_bwd_args;
+int ag_gfront_stack_bwd_ok(int B, int S, int fs, int nl, int n_cu);
+int64_t ag_gfront_stack_bwd_ws_bytes(int B, int S, int fs, int nl);
+int ag_gfront_stack_bwd(const ag_front_stack_bwd_args* a, void* stream);
+
 /* One fused backward step of the Generator front (audiogan.py:428-460: LSTMCell -> tanh(Linear) fed back), frame t:
  *   gx     = dxa * (1 - x_t^2)                        d(pre-tanh) of the projection, stored to gx_out [B,Kp]
  *   dh     = dh_acc + gx * w_proj                      w_proj [Kp = frame size, H]; dh_acc [B,H] rows, pitch lddh
