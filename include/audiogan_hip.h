@@ -404,7 +404,7 @@ int ag_lstm_seq_bwd_persist(const float* const* gates, const float* const* whh, 
                             int64_t ws_bytes, int T, int B, int H, int ndir, int n_cu, void* stream);
 
 /* The Generator front's whole frame loop (audiogan.py:428-460: one recurrent cell + tanh(proj) fed back) as ONE
- * persistent launch with every weight resident in registers (csrc/lstm_persist.hip), in two modes:
+ * persistent launch with every weight resident in registers (csrc/front_persist.hip), in two modes:
  *   training (gen 0): `gates` comes in as the z / c part of the pre-activations (one GEMM over all frames) and goes out
  *     activated; the history the backward needs (hs, cs or gh, xt) is written beside the frames x.
  *   generation (gen 1, Generator.generate): the frame loop of a SAMPLE, trains nothing and keeps no history - `gates` is only
@@ -456,7 +456,7 @@ int64_t ag_gfront_persist_ws_bytes(int B, int S, int fs);
 int ag_gfront_fwd(const ag_front_fwd_args* a, void* stream);
 
 /* The frame loop of a STACKED front (audiogan.py:382-385, :441-442: nl LSTMCell layers, 2 <= nl <= 8, under one projection
- * and one stop head, both fed by the top layer's h) as ONE persistent launch (csrc/lstm_persist.hip), in the two modes of
+ * and one stop head, both fed by the top layer's h) as ONE persistent launch (csrc/front_stack.hip), in the two modes of
  * ag_gfront_fwd.  Frame t: layer 0 takes [x_{t-1}, zc_t] and its own h_{0,t-1}; layer l >= 1 takes h_{l-1,t} and its own
  * h_{l,t-1}; x_t = tanh(h_{nl-1,t} W_p^T + b_p); (generation) s_t = h_{nl-1,t} . w_s + b_s, with the stop draws, the exit
  * rule and the outputs s, first, t_run exactly as ag_gfront_fwd states them.  LSTMCell only.  fp32 MFMA; in bf16 mode
@@ -532,7 +532,7 @@ int ag_gfront_bwd_persist_ok(int B, int S, int fs, int n_cu);
 int ag_gfront_bwd(const ag_front_bwd_args* a, void* stream);
 
 /* The BACKWARD through time of a STACKED front (2 <= nl <= 8 LSTMCell layers, L = nl - 1 the top one) in one persistent
- * launch (csrc/lstm_persist.hip).  Per frame t = T-1 .. 0, every term of frame T being zero:
+ * launch (csrc/front_stack.hip).  Per frame t = T-1 .. 0, every term of frame T being zero:
  *   gx_t     = (dx_ext[t] + dg_{0,t+1} W_x)(1 - x_t^2)                     -> dxt[t]
  *   dh_{L,t} = dh_ext[t] + dg_{L,t+1} W_hh_L + gx_t W_p                    (the stop head's gradient lands on the top layer only)
  *   dh_{l,t} = dg_{l,t+1} W_hh_l + dg_{l+1,t} W_ih_{l+1}                   l < L

@@ -17,7 +17,7 @@ import torch
 from tests import recurrent_cases as RC
 from tests.recurrent_cases import FRONT_FZ, Framed, bound, err_of, margin_of, same_bits      # noqa: F401  (re-exported)
 
-GEN_LAG = 1      # lstm_persist.hip: the exit test before frame t + 1 reads the decisions of frame t - GEN_LAG
+GEN_LAG = 1      # csrc/front_parts.h: the exit test before frame t + 1 reads the decisions of frame t - GEN_LAG
 
 # (nl, S, fs, B, T): every one takes the stacked launch on 256 CUs (asserted with ag_gfront_stack_ok by the tests)
 CASES = [dict(id=i, nl=nl, S=S, fs=fs, B=B, T=T, why=why) for i, (nl, S, fs, B, T, why) in enumerate([

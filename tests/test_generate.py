@@ -12,7 +12,7 @@ import torch
 from oracle import audiogan_oracle as O
 from tests import kernel_model
 
-GEN_LAG = 1      # lstm_persist.hip: the exit test before frame t + 1 reads the decisions of frame t - GEN_LAG
+GEN_LAG = 1      # csrc/front_parts.h: the exit test before frame t + 1 reads the decisions of frame t - GEN_LAG
 
 
 def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=None):

@@ -7,7 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-GEN_LAG = 1      # lstm_persist.hip
+GEN_LAG = 1      # csrc/front_parts.h
 
 
 @pytest.fixture(scope='module')
