@@ -184,6 +184,8 @@ SIGNATURES = {
     'ag_ltas_ws_numel': (i64, [C.c_int, C.c_int]),
     'ag_ltas_power': (C.c_int, [vp, i64, vp, vp, vp, C.c_int, C.c_int, vp]),
     'ag_score_accum': (C.c_int, [vp, i64, i64, vp, f32, C.c_int, vp, C.c_int, C.c_int, vp]),
+    'ag_melcep_frames': (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    'ag_dtw_cost': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
 }
 
 

@@ -6,6 +6,7 @@ the kernel on torch's current HIP stream.  Nothing here computes on the host and
 is no fallback: a non-CUDA tensor raises."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2012,4 +2013,103 @@ def score_accum(cls, nframes, target, positive, acc):
 
 
 for _n in ('ltas_power', 'score_accum'):
+    _instrument(_n, _work_named)
+
+
+# ------------------------------------------------------------------------------------
+# aligned distance (evaluate.Evaluator(aligned=True), evaluate.aligned_distance): per-frame mel cepstra, DTW totals
+# ------------------------------------------------------------------------------------
+MEL_BANDS, MEL_NCEP, CEP_WIDTH = 24, 13, 16          # columns 0..12 of a 16-float row hold the cepstra, 13..15 are zero
+DTW_MAX_FRAMES = 1024
+_ALIGN_TABLES = {}
+
+
+def lt_frames(L):
+    """frames of a clip of L samples (256 samples, hop 128; a clip shorter than one frame is one zero-padded frame)"""
+    return (int(L) - 256) // 128 + 1 if L >= 256 else 1
+
+
+def _mel64(sr, bands):
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)          # noqa: E731
+    edges = 700.0 * (10.0 ** (np.linspace(0.0, mel(sr / 2.0), bands + 2) / 2595.0) - 1.0)
+    f = np.arange(LTAS_BINS, dtype=np.float64) * sr / 256.0
+    lo, mid, hi = edges[:-2, None], edges[1:-1, None], edges[2:, None]
+    return np.maximum(0.0, np.minimum((f[None, :] - lo) / (mid - lo), (hi - f[None, :]) / (hi - mid)))
+
+
+def _dct64(bands, ncep):
+    q, m = np.arange(ncep, dtype=np.float64)[:, None], np.arange(bands, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / bands) * np.cos(np.pi * q * (m + 0.5) / bands)
+
+
+def _align_table(key, make, device):
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = key + (str(device),)
+    if key not in _ALIGN_TABLES:
+        _ALIGN_TABLES[key] = torch.from_numpy(make().astype(np.float32)).to(device)
+    return _ALIGN_TABLES[key]
+
+
+def mel_table(sr=8000, bands=MEL_BANDS, device='cuda'):
+    """[bands, 129] fp32: triangles of peak 1 over the bin frequencies k sr / 256, edges equally spaced in
+    mel(f) = 2595 log10(1 + f / 700) on [0, mel(sr / 2)]; evaluated in float64, rounded once; cached per device"""
+    return _align_table(('mel', int(sr), int(bands)), lambda: _mel64(float(sr), int(bands)), device)
+
+
+def dct_table(bands=MEL_BANDS, ncep=MEL_NCEP, device='cuda'):
+    """[ncep, bands] fp32: sqrt(2 / bands) cos(pi q (m + 0.5) / bands); evaluated in float64, rounded once; cached per device"""
+    return _align_table(('dct', int(bands), int(ncep)), lambda: _dct64(int(bands), int(ncep)), device)
+
+
+def melcep_frames(x, lens, mel=None, dct=None, cep=None, nframes=None, power=None):
+    """x [B, L] and lens as ``ltas_power`` takes them -> cep [B, F, 16] fp32, F = lt_frames(L): per frame (256 samples, hop 128,
+    periodic Hann) the 13 mel cepstra c[q] = sum_m dct[q, m] log(sum_k mel[m, k] |X[k]|^2 + 1e-10) in columns 0..12, zeros
+    in 13..15.  ``mel`` [24, 129] / ``dct`` [13, 24]: device tables (default: ``mel_table`` / ``dct_table``); ``nframes``: an
+    int32 [B] tensor that receives the frame counts; ``power``: a [B, F, 129] tensor that receives |X[k]|^2 per frame.
+    Rows at or past a clip's frame count are not written in either output.  The DFT is an fp32 MFMA product
+    (ag_melcep_frames: one launch)."""
+    _chk(x, 'x'); _chk(lens, 'lens', torch.int64); _chk(nframes, 'nframes', torch.int32)
+    assert x.dim() == 2, tuple(x.shape)
+    B, L = x.shape
+    ld = _rows(x, 'x', B, L)
+    F = lt_frames(L)
+    mel = mel_table(device=x.device) if mel is None else mel
+    dct = dct_table(device=x.device) if dct is None else dct
+    _chk(mel, 'mel'); _chk(dct, 'dct')
+    assert mel.is_contiguous() and tuple(mel.shape) == (MEL_BANDS, LTAS_BINS), tuple(mel.shape)
+    assert dct.is_contiguous() and tuple(dct.shape) == (MEL_NCEP, MEL_BANDS), tuple(dct.shape)
+    assert lens is None or (lens.is_contiguous() and lens.numel() == B)
+    assert nframes is None or (nframes.is_contiguous() and nframes.numel() == B)
+    if cep is None:
+        cep = torch.empty(B, F, CEP_WIDTH, dtype=torch.float32, device=x.device)
+    _chk(cep, 'cep'); _chk(power, 'power')
+    assert cep.is_contiguous() and tuple(cep.shape) == (B, F, CEP_WIDTH), tuple(cep.shape)
+    assert power is None or (power.is_contiguous() and tuple(power.shape) == (B, F, LTAS_BINS)), tuple(power.shape)
+    check(lib.ag_melcep_frames(_p(x), ld, _p(lens), _p(mel), _p(dct), _p(cep), _p(nframes), _p(power), B, L, _stream()),
+          'ag_melcep_frames')
+    return cep
+
+
+def dtw_cost(cep_a, nf_a, cep_b, nf_b, out=None):
+    """cep_a [B, Fa, 16], cep_b [B, Fb, 16] (``melcep_frames`` rows), nf_a / nf_b int32 [B] -> out [B] fp32: the total of the
+    symmetric dynamic-time-warping recursion D(i, j) = min(D(i-1, j) + d, D(i, j-1) + d, D(i-1, j-1) + 2 d), D(0, 0) = 2 d,
+    d the Euclidean distance of columns 1..12, at (n - 1, m - 1).  Every path has weight n + m: divide by it.  Rows at or
+    past the counts and columns 0, 13..15 are never read; at most 1024 frames a side (ag_dtw_cost: one launch)."""
+    _chk(cep_a, 'cep_a'); _chk(cep_b, 'cep_b'); _chk(nf_a, 'nf_a', torch.int32); _chk(nf_b, 'nf_b', torch.int32)
+    assert cep_a.dim() == 3 and cep_b.dim() == 3 and cep_a.size(2) == cep_b.size(2) == CEP_WIDTH, (cep_a.shape, cep_b.shape)
+    B, Fa, Fb = cep_a.size(0), cep_a.size(1), cep_b.size(1)
+    assert cep_b.size(0) == B and cep_a.is_contiguous() and cep_b.is_contiguous()
+    assert nf_a is None or (nf_a.is_contiguous() and nf_a.numel() == B)
+    assert nf_b is None or (nf_b.is_contiguous() and nf_b.numel() == B)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=cep_a.device)
+    _chk(out, 'out')
+    assert out.is_contiguous() and tuple(out.shape) == (B,), tuple(out.shape)
+    check(lib.ag_dtw_cost(_p(cep_a), _p(nf_a), _p(cep_b), _p(nf_b), _p(out), B, Fa, Fb, _stream()), 'ag_dtw_cost')
+    return out
+
+
+for _n in ('melcep_frames', 'dtw_cost'):
     _instrument(_n, _work_named)

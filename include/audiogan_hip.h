@@ -764,6 +764,38 @@ int ag_ltas_power(const float* x, int64_t ldx, const int64_t* lens_i64, float* o
 int ag_score_accum(const float* x, int64_t sxb, int64_t sxt, const int64_t* nframes_i64, float target, int positive,
                    double* acc, int B, int T, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Aligned distance of the held-out evaluation (evaluate.Evaluator(aligned=True), evaluate.aligned_distance): per-frame mel
+ * cepstra and the dynamic-time-warping total between two cepstral sequences (csrc/evalalign.hip).  Both kernels are fp32
+ * whatever ag_set_precision says, add in a fixed order and use no atomics: two runs give the same bits.  Both launchers
+ * refuse bad arguments before their first HIP call.
+ *   ag_melcep_frames x, ldx, lens, n_b and the framing exactly as ag_ltas_power: 256-sample periodic-Hann frames at hop 128,
+ *                    j = 0 .. (n_b - 256) / 128 when n_b >= 256, otherwise ONE zero-padded frame; x[b, t] is never read
+ *                    for t >= n_b.  F = the frame count of a clip of L samples is the frame capacity of the outputs.
+ *                    Per frame j < nframes[b]:
+ *                      P[k]  = |X_j[k]|^2, k = 0..128             -> power[b, j, k] ([B, F, 129] contiguous; NULL: not written)
+ *                      E[m]  = sum_k mel[m, k] P[k], m = 0..23     (mel [24, 129] fp32 on the device, weights >= 0)
+ *                      c[q]  = sum_m dct[q, m] logf(E[m] + 1e-10f), q = 0..12   (dct [13, 24] fp32 on the device)
+ *                    -> cep[b, j, 0..12] = c, cep[b, j, 13..15] = 0 ([B, F, 16] contiguous).  nframes_out[b] (int32, may be
+ *                    NULL) = the frame count.  Rows j >= nframes[b] of cep and power are never written.  fp32 sums in
+ *                    ascending index order (a zero mel weight is skipped: it adds nothing).  The transform of a tile of 32
+ *                    frames is an fp32 MFMA product (v_mfma_f32_32x32x2_f32: exact fp32 fma chains) of the windowed,
+ *                    folded frames with twiddles that are cospif values of exact arguments; one launch, no workspace, and
+ *                    a frame's bits do not depend on the tile it falls in.
+ *   ag_dtw_cost      cep_a [B, Fa, 16], cep_b [B, Fb, 16] fp32 contiguous; n = clamp(nf_a[b], 1, Fa), m = clamp(nf_b[b], 1,
+ *                    Fb) (int32; NULL: the capacity).  Rows at or past the counts and columns 0 and 13..15 are never read.
+ *                      d(i, j) = sqrtf(sum_{q = 1..12} (a[i, q] - b[j, q])^2)      (fp32, sqrtf correctly rounded)
+ *                      D(0, 0) = 2 d(0, 0)
+ *                      D(i, j) = min(D(i-1, j) + d, D(i, j-1) + d, D(i-1, j-1) + 2 d) over the predecessors that exist
+ *                    out[b] = D(n-1, m-1), the raw total of the symmetric step pattern: every path has weight n + m, so the
+ *                    caller divides by n + m.  ag_dtw_cost(a, b) and ag_dtw_cost(b, a) give the same bits.
+ *                    Fa, Fb <= 1024 (clips of up to 131200 samples); one workgroup per pair, one thread per row of a.
+ * ------------------------------------------------------------------------- */
+int ag_melcep_frames(const float* x, int64_t ldx, const int64_t* lens_i64, const float* mel, const float* dct, float* cep,
+                     int32_t* nframes_out, float* power, int B, int L, void* stream);
+int ag_dtw_cost(const float* cep_a, const int32_t* nf_a, const float* cep_b, const int32_t* nf_b, float* out, int B, int Fa,
+                int Fb, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
