@@ -186,6 +186,7 @@ SIGNATURES = {
     'ag_score_accum': (C.c_int, [vp, i64, i64, vp, f32, C.c_int, vp, C.c_int, C.c_int, vp]),
     'ag_melcep_frames': (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     'ag_dtw_cost': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    'ag_dtw_pairs': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
 }
 
 

@@ -21,6 +21,8 @@ What a pass measures (``run``), per held-out minibatch, without instance noise a
     both           feature_penalty_fused of the two sets of conv activations      -> feature_penalty (mean over minibatches)
     spectrum       ltas_power(fake) against the real clips' (computed once)       -> ltas_db
     aligned=True   dtw_cost(melcep_frames(fake), melcep_frames(real), computed once)  -> mcd_db
+    crossed=True   dtw_pairs(every fake's cepstra x every real clip's of the minibatch)  -> nn_db, cover_db, word_hit
+    draws=k        k - 1 further fakes per word, dtw_pairs between the draws             -> div_db (beside real_div_db)
 
 ``ltas_db`` is the mean over all clips of sqrt(mean_k (dB_fake[k] - dB_real[k])^2), dB = 10 log10(P + 1e-10) over the 129 bins
 of ``kernels.ltas_power``; fake i and real clip i share their word.  The statistics are accumulated on the device
@@ -37,6 +39,20 @@ the total divided by n + m is a mean over the path that moves continuously with 
 length would jump where two paths tie).  mcd_db = (10 / ln 10) sqrt(2) times the mean of that over all clips - the usual
 mel-cepstral distortion in dB.  It is a distance between ONE fake and ONE real utterance of the word, not a perceptual
 score: two real speakers of the same word are some dB apart as well, and only its trend over training says something.
+
+``crossed`` and ``draws`` (both off by default, both need ``aligned``) ask the two questions one draw per word against one
+real clip cannot answer.  ``crossed``: per held-out minibatch the aligned distance of EVERY fake to EVERY real clip, a [B, B]
+matrix M in dB from one ``kernels.dtw_pairs`` launch (``crossed_scores`` states the rule).  ``nn_db`` is the mean over the
+fakes of their nearest real clip's distance, ``cover_db`` the mean over the real clips of their nearest fake's - a
+generator that says one word for every word keeps ``nn_db`` and loses ``cover_db``.  ``word_hit`` is the share of fakes
+whose nearest real clip carries their own word, and ``word_hit/chance`` the share a blind guess would reach (the mean share
+of the minibatch's real clips that carry the fake's word: 1 / B when all words differ).  This is retrieval among the B words of
+one minibatch, to be read against ``word_hit/chance`` - not speech recognition.  ``draws=k``: k - 1 further (z, u) per
+minibatch, drawn from the private generator AFTER every first draw (so those keep their bits), give k fakes per word;
+``div_db`` is the mean aligned distance between two draws of the same word, over all clips and the k (k - 1) / 2 draw pairs.
+Zero means z does nothing.  Two real utterances of a word are some dB apart as well, so ``div_db`` only means something
+beside ``real_div_db``: the same mean over all pairs of held-out REAL clips that share a word, computed once when the
+evaluator is built (None when no word occurs twice).  The extra fakes get no critic pass.
 
 What the numbers do NOT say: the held-out clips are few and fixed, so the critic numbers are a trend, not an estimate with
 error bars; and a long-term average spectrum is blind to everything temporal - a sample can match it and still be
@@ -58,13 +74,40 @@ from . import kernels as K
 from .extras import feature_penalty_fused
 
 DB_FLOOR = 1e-10
-_ACC_D, _ACC_G, _PEN, _LTAS, _FRAMES, _MCD, _WORDS = 0, 6, 12, 13, 14, 15, 16
+_ACC_D, _ACC_G, _PEN, _LTAS, _FRAMES, _MCD, _NN, _COVER, _HIT, _DIV, _WORDS = 0, 6, 12, 13, 14, 15, 16, 17, 18, 19, 20
 MCD_DB = 10.0 / math.log(10.0) * math.sqrt(2.0)          # the mel-cepstral distance's constant: natural-log cepstra -> dB
 
 
 def power_db(p):
     """10 log10(P + 1e-10) in float64 (the logarithm is taken here, not in the kernel)"""
     return 10.0 * torch.log10(p.double() + DB_FLOOR)
+
+
+def _crossed_sums(M, same):
+    """M [Nf, Nr] float64, same [Nf, Nr] bool -> (sum of the row minima, sum of the column minima, number of rows whose
+    minimum is attained in a column with ``same``), tensors where M lives"""
+    rowmin = M.min(1).values
+    hit = ((M == rowmin[:, None]) & same).any(1)
+    return rowmin.sum(), M.min(0).values.sum(), hit.sum()
+
+
+def crossed_scores(M, same):
+    """M [Nf, Nr]: the distance of fake i to real clip j; same [Nf, Nr] bool: fake i and real clip j carry the same word
+    -> dict(nn_db: mean over i of min_j M, cover_db: mean over j of min_i M, word_hit: the share of fakes i for which some j
+    with same[i, j] ATTAINS the row minimum (a tie with another word's clip counts as a hit), chance: the mean over i of
+    same[i].sum() / Nr - the hit rate of a uniform guess)"""
+    M = torch.as_tensor(M).double()
+    same = torch.as_tensor(same).to(M.device).bool()
+    assert M.dim() == 2 and same.shape == M.shape and M.numel() > 0, (tuple(M.shape), tuple(same.shape))
+    nf, nr = M.shape
+    nn, cover, hit = _crossed_sums(M, same)
+    return dict(nn_db=float(nn) / nf, cover_db=float(cover) / nr, word_hit=float(hit) / nf,
+                chance=float(same.double().sum(1).div(nr).mean()))
+
+
+def _pair_db(total, nf_a, nf_b):
+    """raw DTW totals and the two frame counts (broadcast against each other) -> float64 dB"""
+    return MCD_DB * total.double() / (nf_a + nf_b).double()
 
 
 def finish_scores(a):
@@ -76,21 +119,26 @@ def finish_scores(a):
 
 class Evaluator(object):
     def __init__(self, g, d, e_g, e_d, heldout, batch_size, maxlen, device, batches=4, seed=0, ema=None, on_eval=None,
-                 path=None, aligned=False):
+                 path=None, aligned=False, crossed=False, draws=1):
         """``heldout``: the validation loader ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths,
         keys, cseq, clen]) or a list of such minibatches; ``batches`` of them are taken NOW (see the module text: build the
         evaluator before the training loader's first ``next()`` when this is a loader).  ``ema``: an ``optim.EMA`` - the pass
         runs inside ``ema.applied()``, as samples do.  ``on_eval(result)``: receives every result dict; ``path``: every
         result is appended there as one JSON line with ``kind: 'E'``.  ``aligned``: also measure ``mcd_db``, the
         mel-cepstral distance of every fake along its time-warping path to the real clip of the same word (module text)
-        - the real clips' cepstra are computed now and kept."""
+        - the real clips' cepstra are computed now and kept.  ``crossed`` / ``draws`` (both need ``aligned``): also measure
+        ``nn_db``, ``cover_db``, ``word_hit`` and ``word_hit/chance`` / ``div_db`` and ``real_div_db`` (module text)."""
         self.g, self.d, self.e_g, self.e_d = g, d, e_g, e_d
         self.B, self.maxlen, self.dev = int(batch_size), maxlen, torch.device(device)
         self.ema, self.on_eval, self.path = ema, on_eval, path
         fs = g._frame_size
         self.nframes = (maxlen + fs - 1) // fs
         self.L = self.nframes * fs
-        self.aligned = bool(aligned)
+        self.aligned, self.crossed, self.draws = bool(aligned), bool(crossed), int(draws)
+        if self.draws < 1 or self.draws != draws:
+            raise ValueError('Evaluator(draws=%r): a whole number of draws per word, 1 or more' % (draws,))
+        if (self.crossed or self.draws > 1) and not self.aligned:
+            raise ValueError('Evaluator(crossed=%r, draws=%r) compares cepstra: it needs aligned=True' % (crossed, draws))
         if self.aligned and K.lt_frames(self.L) > K.DTW_MAX_FRAMES:
             raise ValueError('Evaluator(aligned=True): clips of %d samples have %d frames; kernels.dtw_cost takes at most %d'
                              % (self.L, K.lt_frames(self.L), K.DTW_MAX_FRAMES))
@@ -113,6 +161,31 @@ class Evaluator(object):
                 nf = torch.empty(self.B, dtype=torch.int32, device=self.dev)
                 self.set[-1].update(real_cep=K.melcep_frames(real, real_len, nframes=nf), real_nf=nf)
         self.clips = self.B * batches
+        self._chance = self.real_div_db = None
+        if self.crossed or self.draws > 1:
+            words = [[tuple(np.asarray(mb[5])[b, :int(np.asarray(mb[6])[b])].tolist()) for b in range(self.B)] for mb in took]
+        if self.crossed:
+            for mb, w in zip(self.set, words):
+                same = np.array([[a == b for b in w] for a in w], dtype=bool)
+                mb['same'] = self._up(same, torch.bool)
+            self._chance = float(np.mean([sum(a == b for b in w) / float(self.B) for w in words for a in w]))
+        if self.draws > 1:
+            for mb in self.set:          # after every first draw: those keep the bits of an evaluator with draws=1
+                mb['more'] = [(torch.randn(self.B, self.nframes, g._noise_size, device=self.dev, generator=rng),
+                               torch.rand(self.nframes, self.B, device=self.dev, generator=rng)) for _ in range(self.draws - 1)]
+            # draw pairs (p < q) of every clip, as rows of the bank of draws * B fakes a pass fills
+            pq = [(p * self.B + b, q * self.B + b) for p in range(self.draws) for q in range(p + 1, self.draws)
+                  for b in range(self.B)]
+            self._pairs = tuple(self._up(np.array(c, dtype=np.int32), torch.int32) for c in zip(*pq))
+            # the yardstick: all pairs i < j of held-out real clips that share a word, one launch over the concatenated cepstra
+            flat = [w for ws in words for w in ws]
+            ij = [(i, j) for i in range(len(flat)) for j in range(i + 1, len(flat)) if flat[i] == flat[j]]
+            if ij:
+                cep = torch.cat([mb['real_cep'] for mb in self.set])
+                nf = torch.cat([mb['real_nf'] for mb in self.set])
+                ia, ib = (self._up(np.array(c, dtype=np.int32), torch.int32) for c in zip(*ij))
+                tot = K.dtw_pairs(cep, nf, cep, nf, ia, ib)
+                self.real_div_db = float(_pair_db(tot, nf[ia.long()], nf[ib.long()]).mean())
         self._buf = torch.zeros(_WORDS, dtype=torch.float64, device=self.dev)
 
     def _up(self, a, dtype):
@@ -120,9 +193,13 @@ class Evaluator(object):
 
     def run(self, gen_iter=None, dis_iter=None, parts=False):
         """one pass over the fixed held-out set -> dict(loss_d, acc_d, cls_d/mean, cls_d/std, loss_g, acc_g, cls_g/mean,
-        cls_g/std, feature_penalty, ltas_db, frames/mean, clips, gen_iter, dis_iter; with ``aligned`` also mcd_db).
+        cls_g/std, feature_penalty, ltas_db, frames/mean, clips, gen_iter, dis_iter; with ``aligned`` also mcd_db, with
+        ``crossed`` nn_db, cover_db, word_hit and word_hit/chance, with ``draws`` of 2 or more div_db and real_div_db).
         ``parts=True``: returns (dict, list) with, per minibatch, the waves, lengths, logits, conv activations and powers the
-        numbers were computed from (with ``aligned`` also cep, nf, real_cep, real_nf and dtw, the raw totals)."""
+        numbers were computed from (with ``aligned`` also cep, nf, real_cep, real_nf and dtw, the raw totals; with
+        ``crossed`` cross, the raw [B, B] totals fake x real, and same; with ``draws`` bank_cep [draws * B, F, 16] and bank_nf,
+        the cepstra and counts of every draw (draw p of clip b in row p * B + b), and pair_ia, pair_ib, pair_dtw: the rows
+        compared and their raw totals)."""
         g, d, e_g, e_d = self.g, self.d, self.e_g, self.e_d
         fs = g._frame_size
         buf, kept = self._buf, []
@@ -161,6 +238,30 @@ class Evaluator(object):
                     buf[_MCD] += (dtw.double() / (nf + mb['real_nf']).double()).sum()
                     if parts:
                         kept[-1].update(cep=cep, nf=nf, real_cep=mb['real_cep'], real_nf=mb['real_nf'], dtw=dtw)
+                if self.crossed:
+                    cross = K.dtw_pairs(cep, nf, mb['real_cep'], mb['real_nf'])
+                    nn, cover, hit = _crossed_sums(_pair_db(cross, nf[:, None], mb['real_nf'][None, :]), mb['same'])
+                    buf[_NN] += nn
+                    buf[_COVER] += cover
+                    buf[_HIT] += hit
+                    if parts:
+                        kept[-1].update(cross=cross, same=mb['same'])
+                if self.draws > 1:
+                    # the extra fakes: no critic pass; every draw's cepstra go into one bank at the widest draw's capacity
+                    # (rows past a clip's count are never read, so what the bank holds there does not matter)
+                    ceps, nfs = [cep], torch.empty(self.draws * self.B, dtype=torch.int32, device=self.dev)
+                    nfs[:self.B] = nf
+                    for q, (z, u) in enumerate(mb['more'], 1):
+                        more, _, _, more_len = g.generate(embed_g, z=z, u=u)
+                        ceps.append(K.melcep_frames(more, more_len, nframes=nfs[q * self.B:(q + 1) * self.B]))
+                    bank = torch.zeros(self.draws * self.B, max(c.size(1) for c in ceps), K.CEP_WIDTH, device=self.dev)
+                    for q, c in enumerate(ceps):
+                        bank[q * self.B:(q + 1) * self.B, :c.size(1)] = c
+                    ia, ib = self._pairs
+                    tot = K.dtw_pairs(bank, nfs, bank, nfs, ia, ib)
+                    buf[_DIV] += _pair_db(tot, nfs[ia.long()], nfs[ib.long()]).sum()
+                    if parts:
+                        kept[-1].update(bank_cep=bank, bank_nf=nfs, pair_ia=ia, pair_ib=ib, pair_dtw=tot)
             host = buf.cpu().tolist()          # the pass's ONE copy to the host
         res = {}
         for tag, o in (('d', _ACC_D), ('g', _ACC_G)):
@@ -171,6 +272,12 @@ class Evaluator(object):
         res['frames/mean'] = host[_FRAMES] / self.clips
         if self.aligned:
             res['mcd_db'] = MCD_DB * host[_MCD] / self.clips
+        if self.crossed:
+            res['nn_db'], res['cover_db'] = host[_NN] / self.clips, host[_COVER] / self.clips
+            res['word_hit'], res['word_hit/chance'] = host[_HIT] / self.clips, self._chance
+        if self.draws > 1:
+            res['div_db'] = host[_DIV] / (self.clips * (self.draws * (self.draws - 1) // 2))
+            res['real_div_db'] = self.real_div_db
         res['clips'] = self.clips
         res['gen_iter'] = None if gen_iter is None else int(gen_iter)
         res['dis_iter'] = None if dis_iter is None else int(dis_iter)
@@ -196,3 +303,18 @@ def aligned_distance(wave_a, len_a, wave_b, len_b):
     cep_a = K.melcep_frames(wave_a, len_a, nframes=nf_a)
     cep_b = K.melcep_frames(wave_b, len_b, nframes=nf_b)
     return MCD_DB * K.dtw_cost(cep_a, nf_a, cep_b, nf_b).double() / (nf_a + nf_b).double()
+
+
+def aligned_distance_matrix(wave_a, len_a, wave_b, len_b):
+    """wave_a [Na, La], wave_b [Nb, Lb] as ``aligned_distance`` takes them -> [Na, Nb] float64: ``aligned_distance`` of every
+    clip of a against every clip of b, MCD_DB total / (n_i + m_j) - two ``melcep_frames`` launches and one ``dtw_pairs``
+    launch, with the bits ``aligned_distance`` gives pair by pair.  At most 1024 frames (131200 samples) a side."""
+    for w in (wave_a, wave_b):
+        if K.lt_frames(w.size(1)) > K.DTW_MAX_FRAMES:
+            raise ValueError('aligned_distance_matrix: clips of %d samples have more than %d frames'
+                             % (w.size(1), K.DTW_MAX_FRAMES))
+    nf_a = torch.empty(wave_a.size(0), dtype=torch.int32, device=wave_a.device)
+    nf_b = torch.empty(wave_b.size(0), dtype=torch.int32, device=wave_a.device)
+    cep_a = K.melcep_frames(wave_a, len_a, nframes=nf_a)
+    cep_b = K.melcep_frames(wave_b, len_b, nframes=nf_b)
+    return _pair_db(K.dtw_pairs(cep_a, nf_a, cep_b, nf_b), nf_a[:, None], nf_b[None, :])

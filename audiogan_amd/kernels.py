@@ -2111,5 +2111,35 @@ def dtw_cost(cep_a, nf_a, cep_b, nf_b, out=None):
     return out
 
 
-for _n in ('melcep_frames', 'dtw_cost'):
+def dtw_pairs(cep_a, nf_a, cep_b, nf_b, ia=None, ib=None, out=None):
+    """cep_a [Na, Fa, 16], cep_b [Nb, Fb, 16] (``melcep_frames`` rows), nf_a [Na] / nf_b [Nb] int32: two BANKS of sequences.
+    ``ia``, ``ib`` (int32 [P], both or neither) -> out [P] fp32, out[p] = the ``dtw_cost`` total of a[ia[p]] against b[ib[p]]
+    (the kernel clamps the indices into the banks); without them -> out [Na, Nb], every a against every b.  The bits are
+    those ``dtw_cost`` gives for the same two sequences, and no gathered copy of a bank is made.  Capacities of at most 64
+    frames on one side and 256 on the other run one wave per pair; anything else, up to 1024 frames a side, one workgroup
+    per pair (ag_dtw_pairs: one launch)."""
+    _chk(cep_a, 'cep_a'); _chk(cep_b, 'cep_b'); _chk(nf_a, 'nf_a', torch.int32); _chk(nf_b, 'nf_b', torch.int32)
+    _chk(ia, 'ia', torch.int32); _chk(ib, 'ib', torch.int32)
+    assert cep_a.dim() == 3 and cep_b.dim() == 3 and cep_a.size(2) == cep_b.size(2) == CEP_WIDTH, (cep_a.shape, cep_b.shape)
+    Na, Fa, Nb, Fb = cep_a.size(0), cep_a.size(1), cep_b.size(0), cep_b.size(1)
+    assert cep_a.is_contiguous() and cep_b.is_contiguous()
+    assert nf_a is None or (nf_a.is_contiguous() and nf_a.numel() == Na)
+    assert nf_b is None or (nf_b.is_contiguous() and nf_b.numel() == Nb)
+    if (ia is None) != (ib is None):
+        raise ValueError('audiogan_amd: dtw_pairs takes ia and ib together or neither')
+    if ia is None:
+        shape = (Na, Nb)
+    else:
+        assert ia.dim() == 1 and ia.is_contiguous() and ib.is_contiguous() and ib.shape == ia.shape, (ia.shape, ib.shape)
+        shape = (ia.numel(),)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=cep_a.device)
+    _chk(out, 'out')
+    assert out.is_contiguous() and tuple(out.shape) == shape, (tuple(out.shape), shape)
+    check(lib.ag_dtw_pairs(_p(cep_a), _p(nf_a), Na, Fa, _p(cep_b), _p(nf_b), Nb, Fb, _p(ia), _p(ib), _p(out), out.numel(),
+                           _stream()), 'ag_dtw_pairs')
+    return out
+
+
+for _n in ('melcep_frames', 'dtw_cost', 'dtw_pairs'):
     _instrument(_n, _work_named)

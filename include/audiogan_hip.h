@@ -796,6 +796,30 @@ int ag_melcep_frames(const float* x, int64_t ldx, const int64_t* lens_i64, const
 int ag_dtw_cost(const float* cep_a, const int32_t* nf_a, const float* cep_b, const int32_t* nf_b, float* out, int B, int Fa,
                 int Fb, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ag_dtw_pairs (csrc/evalpairs.hip): the total of ag_dtw_cost for P pairs drawn from two BANKS of sequences, without
+ * gathered copies (evaluate.Evaluator(crossed=True, draws=k), evaluate.aligned_distance_matrix).
+ *   cep_a [Na, Fa, 16], cep_b [Nb, Fb, 16] fp32 contiguous rows of ag_melcep_frames; nf_a [Na], nf_b [Nb] int32 counts
+ *   (NULL: the capacity).  ia, ib: int32 [P] on the device, both given or both NULL.
+ *     lists     out[p] = the DTW total of a[clamp(ia[p], 0, Na-1)] against b[clamp(ib[p], 0, Nb-1)] - the kernel clamps: a
+ *               wrong index is a wrong pair, never an address outside the banks
+ *     NULL      the cross product: P = Na Nb and out[i Nb + j] is pair (i, j)
+ *   under exactly the contract of ag_dtw_cost (the same recursion, counts clamped to [1, capacity], columns 1..12 only, rows
+ *   at or past the counts never read), and with THE BITS ag_dtw_cost returns for the same two sequences.
+ *   Two forms, chosen on the host from the capacities alone:
+ *     wave form       min(Fa, Fb) <= 64 and max(Fa, Fb) <= 256: one wave per pair, four pairs per 256-thread workgroup, the
+ *                     longer side in the wave's own slice of dynamic LDS (4 * F * 48 bytes <= 48 KB), no barrier in the
+ *                     step loop; the side of at most 64 frames supplies the rows (the sides are exchanged when that is b;
+ *                     the output layout does not change)                                     "dtw_pairs_wave_kernel"
+ *     workgroup form  otherwise: the scheme of ag_dtw_cost with pair indices and Fb * 48 bytes of dynamic LDS
+ *                                                                                            "dtw_pairs_wg_kernel"
+ *   No atomics, no spin, no dependency between workgroups, trip counts n + m - 1 <= 2047: two runs give the same bits.
+ *   Refused from host code before any HIP call (AG_ERR_ARG): null cep_a, cep_b or out; exactly one of ia / ib; P <= 0 or
+ *   P > 2^24; NULL lists with P != Na Nb; Na or Nb outside 1..65535; Fa or Fb outside 1..1024.
+ * ------------------------------------------------------------------------- */
+int ag_dtw_pairs(const float* cep_a, const int32_t* nf_a, int Na, int Fa, const float* cep_b, const int32_t* nf_b, int Nb,
+                 int Fb, const int32_t* ia, const int32_t* ib, float* out, int P, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
