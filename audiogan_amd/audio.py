@@ -1,10 +1,22 @@
-"""Audio out: what the reference's summaries write with ``librosa.output.write_wav(wav_file, sample, sr=8000)``
-(audiogan.py:655-667) - a mono WAV file of 32-bit IEEE floats (format tag 3) - with the standard library only."""
+"""Audio out and in.
+
+Out: what the reference's summaries write with ``librosa.output.write_wav(wav_file, sample, sr=8000)``
+(audiogan.py:655-667) - a mono WAV file of 32-bit IEEE floats (format tag 3) - with the standard library only.
+
+In: what the reference's preprocessing reads with ``librosa.load(wav, sr=8000)`` (preprocess.py:24,
+preprocess-fisher.py:232): ``read_wav`` (RIFF WAV, standard library and numpy), and a polyphase windowed-sinc resampler to
+the models' 8 kHz - ``resample_bank`` designs the filter bank on the host in float64, ``resample64`` is the rule in float64
+numpy (the path without a GPU, and the reference of every test), ``resample`` runs it on the device through
+``kernels.resample_poly`` (ag_resample_poly), in chunks."""
+import math
 import struct
+import warnings
 
 import numpy as np
 
+WAVE_FORMAT_PCM = 1
 WAVE_FORMAT_IEEE_FLOAT = 3
+WAVE_FORMAT_EXTENSIBLE = 0xFFFE
 
 
 def write_wav(path, samples, sr=8000):
@@ -21,3 +33,245 @@ def write_wav(path, samples, sr=8000):
             b'data' + struct.pack('<I', len(data)) + data)
     with open(path, 'wb') as f:
         f.write(b'RIFF' + struct.pack('<I', len(body)) + body)
+
+
+def read_wav(path):
+    """-> (data [frames, channels], sr).  ``data`` is int16 for 16-bit PCM and float32 for everything else: 8-bit unsigned
+    as (v - 128) / 128, 24-bit / 2^23, 32-bit / 2^31, IEEE float 32 / 64 unchanged in value.  Format tags 1, 3 and 0xFFFE
+    (extensible: the tag is the first two bytes of the sub-format); unknown chunks are skipped, the pad byte after an
+    odd-sized chunk is honoured, a ``data`` size of 0 or 0xFFFFFFFF means "to the end of the file", and a truncated file
+    gives its whole frames.  Anything else raises ValueError naming the file and the reason."""
+    def bad(why):
+        return ValueError('%s: %s' % (path, why))
+
+    with open(path, 'rb') as f:
+        raw = f.read()
+    if len(raw) < 12 or raw[:4] != b'RIFF' or raw[8:12] != b'WAVE':
+        raise bad('not a RIFF/WAVE file')
+    pos, fmt = 12, None
+    while pos + 8 <= len(raw):
+        cid, size = raw[pos:pos + 4], struct.unpack_from('<I', raw, pos + 4)[0]
+        pos += 8
+        if cid == b'fmt ':
+            if size < 16 or pos + 16 > len(raw):
+                raise bad('a fmt chunk of %d bytes' % size)
+            tag, channels, sr, _, block, bits = struct.unpack_from('<HHIIHH', raw, pos)
+            if tag == WAVE_FORMAT_EXTENSIBLE:
+                if size < 26 or pos + 26 > len(raw):
+                    raise bad('an extensible fmt chunk of %d bytes' % size)
+                tag = struct.unpack_from('<H', raw, pos + 24)[0]
+            fmt = (tag, channels, sr, bits)
+        elif cid == b'data':
+            if fmt is None:
+                raise bad('no fmt chunk before data')
+            tag, channels, sr, bits = fmt
+            if tag not in (WAVE_FORMAT_PCM, WAVE_FORMAT_IEEE_FLOAT):
+                raise bad('format tag 0x%04X is compressed or unknown (PCM and IEEE float are read)' % tag)
+            if channels == 0:
+                raise bad('zero channels')
+            kinds = {(WAVE_FORMAT_PCM, 8): 'u1', (WAVE_FORMAT_PCM, 16): '<i2', (WAVE_FORMAT_PCM, 24): None,
+                     (WAVE_FORMAT_PCM, 32): '<i4', (WAVE_FORMAT_IEEE_FLOAT, 32): '<f4', (WAVE_FORMAT_IEEE_FLOAT, 64): '<f8'}
+            if (tag, bits) not in kinds:
+                raise bad('%d bits per sample with format tag %d' % (bits, tag))
+            if size == 0 or size == 0xFFFFFFFF:
+                size = len(raw) - pos
+            body = raw[pos:pos + size]
+            frame = channels * bits // 8
+            frames = len(body) // frame
+            body = body[:frames * frame]
+            if (tag, bits) == (WAVE_FORMAT_PCM, 24):
+                b3 = np.frombuffer(body, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+                v = b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)
+                v = np.where(v >= 1 << 23, v - (1 << 24), v)
+                data = (v.astype(np.float64) / float(1 << 23)).astype(np.float32)
+            else:
+                v = np.frombuffer(body, dtype=kinds[(tag, bits)])
+                if bits == 16:
+                    data = v.astype(np.int16)
+                elif bits == 8:
+                    data = ((v.astype(np.float64) - 128.0) / 128.0).astype(np.float32)
+                elif tag == WAVE_FORMAT_PCM:
+                    data = (v.astype(np.float64) / float(1 << 31)).astype(np.float32)
+                else:
+                    data = v.astype(np.float32)
+            return np.ascontiguousarray(data.reshape(frames, channels)), int(sr)
+        pos += size + (size & 1)
+    raise bad('no data chunk' if fmt is not None else 'no fmt chunk')
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# resampling: y[N] = sum_t bank[p, t] x[base - half + t],  base = (N M) div L,  p = (N M) mod L
+# ------------------------------------------------------------------------------------------------------------------
+_BANKS = {}
+
+
+def _bank64(L, M, zeros, beta, rolloff):
+    fc = rolloff * min(1.0, L / M)
+    W = zeros / fc
+    half = int(math.ceil(W))
+    t = np.arange(2 * half + 1, dtype=np.float64)[None, :]
+    p = np.arange(L, dtype=np.float64)[:, None]
+    u = t - half - p / L
+    inside = np.abs(u) <= W
+    win = np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (u / W) ** 2))) / np.i0(beta)
+    return half, np.where(inside, fc * np.sinc(fc * u) * win, 0.0)
+
+
+def resample_bank(sr_in, sr_out=8000, zeros=16, beta=8.0, rolloff=0.95, device='cpu'):
+    """-> (L, M, half, bank [L, 2 half + 1] fp32 on ``device``): the Kaiser-windowed sinc at cutoff
+    fc = rolloff min(1, L / M) (in units of half the input rate), ``zeros`` zero crossings a side, W = zeros / fc,
+    half = ceil(W), bank[p, t] = fc sinc(fc u) I0(beta sqrt(1 - (u / W)^2)) / I0(beta) for |u| <= W = zeros / fc,
+    u = t - half - p / L.  Evaluated in float64, rounded once to fp32; cached per (rates, parameters, device)."""
+    import torch
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError('audiogan_amd: sample rates %d -> %d' % (sr_in, sr_out))
+    g = math.gcd(sr_in, sr_out)
+    L, M = sr_out // g, sr_in // g
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (L, M, int(zeros), float(beta), float(rolloff))
+    if key + ('cpu',) not in _BANKS:
+        half, bank = _bank64(L, M, int(zeros), float(beta), float(rolloff))
+        _BANKS[key + ('cpu',)] = (half, torch.from_numpy(bank.astype(np.float32)))
+    if key + (str(device),) not in _BANKS:
+        half, bank = _BANKS[key + ('cpu',)]
+        _BANKS[key + (str(device),)] = (half, bank.to(device))
+    half, bank = _BANKS[key + (str(device),)]
+    return L, M, half, bank
+
+
+def out_count(n, L, M):
+    """samples out of ``n`` frames in: ceil(n L / M)"""
+    return (int(n) * L + M - 1) // M
+
+
+def mono32(x):
+    """[n] or [n, C], int16 or float -> fp32 [n]: the launch's rule - channels added in order in fp32, times fp32(1 / C);
+    int16 values then times 2^-15"""
+    x = np.asarray(x)
+    if x.ndim == 1:
+        x = x[:, None]
+    is16 = x.dtype == np.int16
+    x = x.astype(np.float32)
+    s = x[:, 0].copy()
+    for c in range(1, x.shape[1]):
+        s += x[:, c]
+    s *= np.float32(1.0) / np.float32(x.shape[1])
+    if is16:
+        s *= np.float32(2.0 ** -15)
+    return s
+
+
+_BLOCK = 1 << 14          # rows of one phase gathered at a time in resample64
+
+
+def resample_rule64(x, bank, L, M, out_start=0, n_out=None, in_start=0):
+    """the rule in float64 on given values: ``x`` [n] holds frames in_start .. in_start + n - 1 (zero elsewhere), ``bank``
+    [L, taps]; -> float64 y[out_start .. out_start + n_out - 1] (default: all ceil(n L / M) of a signal starting at 0).
+    Python integers and int64 throughout; vectorised per phase."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    bank = np.asarray(bank, dtype=np.float64)
+    taps = bank.shape[1]
+    half = (taps - 1) // 2
+    n = x.shape[0]
+    if n_out is None:
+        n_out = out_count(n, L, M)
+    y = np.zeros(n_out, dtype=np.float64)
+    if n_out == 0:
+        return y
+    first = (int(out_start) * M) // L - half                      # the lowest frame any output reads
+    last = ((int(out_start) + n_out - 1) * M) // L + half
+    pad = np.zeros(last - first + 1, dtype=np.float64)            # frames first .. last
+    lo, hi = max(first, int(in_start)), min(last + 1, int(in_start) + n)
+    if hi > lo:
+        pad[lo - first:hi - first] = x[lo - int(in_start):hi - int(in_start)]
+    for j0 in range(min(L, n_out)):                                # outputs j0, j0 + L, ..: one phase each
+        N0 = int(out_start) + j0
+        p = (N0 * M) % L
+        cnt = (n_out - j0 + L - 1) // L
+        start = (N0 * M) // L - half - first                       # row k starts at start + k M
+        for k0 in range(0, cnt, _BLOCK):
+            k1 = min(cnt, k0 + _BLOCK)
+            seg = pad[start + k0 * M:start + (k1 - 1) * M + taps]
+            rows = np.lib.stride_tricks.as_strided(seg, shape=(k1 - k0, taps), strides=(M * seg.strides[0], seg.strides[0]),
+                                                   writeable=False)
+            y[j0 + k0 * L:j0 + k1 * L:L] = rows @ bank[p]
+    return y
+
+
+def resample64(x, sr_in, sr_out=8000):
+    """``x`` [n] or [n, C] (int16 or float) -> float64 [ceil(n L / M)]: the rule of ``resample_bank`` in float64 numpy on
+    the fp32-rounded bank and the fp32 mono samples the launch forms.  ``sr_in == sr_out`` returns the mono samples."""
+    mono = mono32(x)
+    if int(sr_in) == int(sr_out):
+        return mono.astype(np.float64)
+    L, M, half, bank = resample_bank(sr_in, sr_out)
+    return resample_rule64(mono, bank.numpy(), L, M)
+
+
+def _as_rows(x):
+    """-> (tensor or array [B, n, C], is_tensor)"""
+    is_t = hasattr(x, 'detach')
+    if not is_t:
+        x = np.asarray(x)
+    nd = x.dim() if is_t else x.ndim
+    if nd == 1:
+        x = x[None, :, None]
+    elif nd == 2:
+        x = x[:, :, None]
+    elif nd != 3:
+        raise ValueError('audiogan_amd: resample takes [n], [B, n] or [B, n, C], got %d axes' % nd)
+    return x, is_t
+
+
+def resample(x, sr_in, sr_out=8000, lens=None, device=None, chunk=1 << 22):
+    """``x`` [n], [B, n] or [B, n, C], numpy or tensor, int16 or float; ``lens``: frames per row (default n) ->
+    (y [B, ceil(n L / M)] float32 on the device used, counts [B] int64 numpy = ceil(lens L / M)); y is zero at and past a
+    row's count.  On a CUDA device, when ``kernels.resample_ok`` admits the rate pair, ag_resample_poly runs in launches of at
+    most ``chunk`` output samples, each fed the window of frames it reads (a host source is uploaded window by window: an
+    hour-long file needs no hour-long device buffer).  Otherwise ``resample64`` on the host - with one warning naming the
+    rate pair when a GPU was there and the launch refused it."""
+    import torch
+    x, is_t = _as_rows(x)
+    B, n, C = (int(s) for s in x.shape)
+    if device is None:
+        device = x.device if is_t and x.is_cuda else ('cuda' if torch.cuda.is_available() else 'cpu')
+    device = torch.device(device)
+    is16 = (x.dtype == torch.int16) if is_t else (x.dtype == np.int16)
+    if not is16:
+        x = x.float() if is_t else x.astype(np.float32, copy=False)
+    ln = np.full(B, n, dtype=np.int64) if lens is None else np.clip(
+        (lens.detach().cpu().numpy() if hasattr(lens, 'detach') else np.asarray(lens)).astype(np.int64).reshape(B), 0, n)
+    g = math.gcd(int(sr_in), int(sr_out))
+    L, M = int(sr_out) // g, int(sr_in) // g
+    counts = (ln * L + M - 1) // M
+    n_max = out_count(n, L, M)
+    on_gpu = device.type == 'cuda'
+    if on_gpu and L != M:
+        from . import kernels as K
+        _, _, half, bank = resample_bank(sr_in, sr_out, device=device)
+        if K.resample_ok(L, M, bank.size(1), C, 1 if is16 else 0):
+            y = torch.empty(B, n_max, dtype=torch.float32, device=device)
+            ln_t = torch.from_numpy(ln)
+            chunk = max(1, int(chunk))
+            for o0 in range(0, n_max, chunk):
+                o1 = min(n_max, o0 + chunk)
+                lo = max(0, (o0 * M) // L - half)
+                hi = max(lo, min(n, ((o1 - 1) * M) // L + half + 1))
+                part = x[:, lo:hi]
+                part = part.to(device) if is_t else torch.from_numpy(np.ascontiguousarray(part)).to(device)
+                K.resample_poly(part, (ln_t - lo).clamp_(0, hi - lo).to(device), bank, L, M, dst=y[:, o0:o1], in_start=lo,
+                                out_start=o0)
+            if lens is not None:          # (the launch writes all n_max entries: past a row's count, the filter's tail)
+                y.masked_fill_(torch.arange(n_max, device=device)[None, :] >= torch.from_numpy(counts).to(device)[:, None], 0.0)
+            return y, counts
+        warnings.warn('audiogan_amd: ag_resample_poly refuses %d -> %d Hz (L %d, %d taps: a bank over 64 KB); resampling '
+                      'on the host in float64' % (sr_in, sr_out, L, bank.size(1)))
+    xh = x.detach().cpu().numpy() if is_t else x
+    y = np.zeros((B, n_max), dtype=np.float32)
+    for b in range(B):
+        if ln[b]:
+            y[b, :counts[b]] = resample64(xh[b, :ln[b]], sr_in, sr_out)
+    return torch.from_numpy(y).to(device), counts

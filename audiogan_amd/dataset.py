@@ -11,7 +11,8 @@ store.  Same function names, arguments and return tuples:
       -> [keys, cseq, clen, samples, lengths] as numpy arrays                          (:76-77)
 
 ``args.dataset`` may be (a) a path to an HDF5 file in the reference's layout -- word-keyed
-datasets of shape (n, maxlen_word), zero padded (needs h5py, which this image lacks), or (b) an
+datasets of shape (n, maxlen_word), zero padded (needs h5py, which this image lacks), (a') a path ending in ``.npz``: the
+same layout as written by ``audiogan_amd.ingest`` from WAV files (``ingest.load_store``, no h5py), or (b) an
 in-memory mapping with the same layout, e.g. ``SyntheticWordDataset`` / ``{'data': array}``,
 which is what bench/tests use (SURVEY.md 8(d) synthetic clips).  Randomness comes from the
 global numpy RNG exactly like the reference (RNG.choice / RNG.permutation).
@@ -52,6 +53,9 @@ class SyntheticWordDataset(dict):
 
 def _open(spec):
     if isinstance(spec, str):
+        if spec.endswith('.npz'):          # a word store written by audiogan_amd.ingest: loaded whole, no h5py
+            from . import ingest
+            return ingest.load_store(spec)
         try:
             import h5py
         except ImportError as e:

@@ -2143,3 +2143,49 @@ def dtw_pairs(cep_a, nf_a, cep_b, nf_b, ia=None, ib=None, out=None):
 
 for _n in ('melcep_frames', 'dtw_cost', 'dtw_pairs'):
     _instrument(_n, _work_named)
+
+
+# ------------------------------------------------------------------------------------
+# ingestion (audio.resample, ingest.build_store): polyphase resampling of ragged rows of PCM frames
+# ------------------------------------------------------------------------------------
+def resample_ok(L, M, taps, channels, kind):
+    """the library's rule for ag_resample_poly: L taps 4 <= 64 KB, taps odd and >= 3, 1..8 channels, kind 0 (fp32) / 1 (int16)"""
+    return bool(lib.ag_resample_ok(int(L), int(M), int(taps), int(channels), int(kind)))
+
+
+def resample_poly(src, src_len, bank, L, M, dst=None, n_out=None, in_start=0, out_start=0):
+    """src [B, n_in] or [B, n_in, C] (fp32 or int16; unit stride along the channels, C along the frames, any row pitch):
+    frames in_start .. in_start + len_b - 1 of B signals, len_b = clamp(src_len[b], 0, n_in) (int64 [B] or None: n_in);
+    ``bank`` [L, taps] fp32 (``audio.resample_bank``).  -> (dst [B, n_out] fp32, counts int64 [B] = ceil(len_b L / M)):
+    dst[b, n] = y[out_start + n], y[N] = sum_t bank[p, t] x[base - half + t], base = (N M) div L, p = (N M) mod L, x the mono
+    signal (channels averaged in fp32, int16 times 2^-15), zero outside the row's frames.  ``n_out`` defaults to
+    ceil(n_in L / M); ALL n_out entries of every row are written - slice at the counts.  A chunk of a signal (its two
+    starts set) has the bits of the whole (ag_resample_poly: one launch)."""
+    kind = 1 if src.dtype == torch.int16 else 0
+    _chk(src, 'src', torch.int16 if kind else torch.float32); _chk(src_len, 'src_len', torch.int64); _chk(bank, 'bank')
+    assert src.dim() in (2, 3), tuple(src.shape)
+    B, n_in = src.size(0), src.size(1)
+    C = src.size(2) if src.dim() == 3 else 1
+    if src.dim() == 3:
+        assert (C == 1 or src.stride(2) == 1) and (n_in <= 1 or src.stride(1) == C), (tuple(src.shape), src.stride())
+    else:
+        assert n_in <= 1 or src.stride(1) == 1, (tuple(src.shape), src.stride())
+    pitch = src.stride(0) if B > 1 else max(src.stride(0), n_in * C)
+    assert bank.dim() == 2 and bank.is_contiguous() and tuple(bank.shape)[0] == L, (tuple(bank.shape), L)
+    assert src_len is None or (src_len.is_contiguous() and src_len.numel() == B)
+    if n_out is None:
+        n_out = dst.size(1) if dst is not None else (n_in * L + M - 1) // M
+    if dst is None:
+        dst = torch.empty(B, n_out, dtype=torch.float32, device=src.device)
+    ldd = _rows(dst, 'dst', B, n_out)
+    check(lib.ag_resample_poly(_p(src), kind, C, pitch, _p(src_len), n_in, int(in_start), _p(bank), int(L), int(M),
+                               bank.size(1), _p(dst), ldd, n_out, int(out_start), B, _stream()), 'ag_resample_poly')
+    if src_len is None:
+        counts = torch.full((B,), (n_in * L + M - 1) // M, dtype=torch.int64, device=src.device)
+    else:
+        counts = (src_len.clamp(0, n_in) * L + (M - 1)) // M
+    return dst, counts
+
+
+for _n in ('resample_poly',):
+    _instrument(_n, _work_named)

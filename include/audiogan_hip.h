@@ -820,6 +820,34 @@ int ag_dtw_cost(const float* cep_a, const int32_t* nf_a, const float* cep_b, con
 int ag_dtw_pairs(const float* cep_a, const int32_t* nf_a, int Na, int Fa, const float* cep_b, const int32_t* nf_b, int Nb,
                  int Fb, const int32_t* ia, const int32_t* ib, float* out, int P, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ag_resample_poly (csrc/resample.hip): polyphase windowed-sinc resampling of ragged rows of PCM frames to the models'
+ * rate (audio.resample, ingest.build_store).  Replaces librosa.load(wav, sr=8000) of the reference's preprocessing
+ * (preprocess.py:24, preprocess-fisher.py:232).  fp32 whatever ag_set_precision says; no atomics, no workspace, one launch.
+ *   src        B rows of interleaved frames, src_pitch ELEMENTS apart; src_kind 0 = fp32, 1 = int16; channels 1..8.
+ *              Row b holds frames in_start .. in_start + len_b - 1 of its signal (absolute frame indices),
+ *              len_b = clamp(src_len[b], 0, n_in) (int64 on the device; NULL: n_in).  Every other frame reads as zero and
+ *              is never loaded.  The mono sample of a frame is (x_0 + .. + x_{C-1}) * (1.0f / C), channels added in order
+ *              in fp32; int16 values are then scaled by 2^-15.
+ *   bank       [L, taps] fp32 contiguous on the device (audio.resample_bank), half = (taps - 1) / 2.
+ *   dst[b, n]  n < n_out, rows dst_pitch floats apart, = y[out_start + n] with
+ *                y[N] = sum_{t = 0}^{taps - 1} bank[p, t] x[base - half + t],  base = (N M) div L,  p = (N M) mod L,
+ *              N M in 64 bits.  Each output is one fmaf chain over t ascending from a zero accumulator, whatever n, b,
+ *              out_start or the tile it falls in: a signal resampled in chunks (a row holding the frames its outputs need
+ *              plus half frames either side, with the two starts set) has the bits of the same signal resampled at once.
+ *              ALL n_out entries of every row are written; the caller slices at ceil(len_b L / M).
+ *   One workgroup per (row, tile of up to 1024 outputs): the tile's input window is converted and downmixed once into
+ *   LDS, the bank sits beside it at its own odd row pitch.                                        "resample_poly_kernel"
+ *   ag_resample_ok: 1 when L, M >= 1, taps is odd and >= 3, L * taps * 4 <= 65536, channels are 1..8 and kind is 0 or 1.
+ *   Refused from host code before any HIP call (AG_ERR_ARG): anything the predicate refuses; a negative size, start or B;
+ *   a null src, dst or bank with work to do; src_pitch < n_in * channels; dst_pitch < n_out; M above 2^20; out_start
+ *   or n_out past 2^40; more than 2^31 - 1 tiles in one launch.  B = 0 or n_out = 0: AG_OK with no launch.
+ * ------------------------------------------------------------------------- */
+int ag_resample_ok(int L, int M, int taps, int channels, int src_kind);
+int ag_resample_poly(const void* src, int src_kind, int channels, long long src_pitch, const long long* src_len,
+                     long long n_in, long long in_start, const float* bank, int L, int M, int taps, float* dst,
+                     long long dst_pitch, long long n_out, long long out_start, int B, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
