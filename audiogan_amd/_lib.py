@@ -190,6 +190,8 @@ SIGNATURES = {
     'ag_resample_ok': (C.c_int, [C.c_int] * 5),
     'ag_resample_poly': (C.c_int, [vp, C.c_int, C.c_int, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, vp, i64, i64, i64,
                                    C.c_int, vp]),
+    'ag_clip_facts': (C.c_int, [vp, vp, vp, vp, vp, i64, vp]),
+    'ag_clip_gather': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp, C.c_int, vp]),
 }
 
 

@@ -2189,3 +2189,57 @@ def resample_poly(src, src_len, bank, L, M, dst=None, n_out=None, in_start=0, ou
 
 for _n in ('resample_poly',):
     _instrument(_n, _work_named)
+
+
+# ------------------------------------------------------------------------------------
+# the device-resident word store (dataset.DeviceWordStore, dataset.ClipBatch): clip facts once, one gather per minibatch
+# ------------------------------------------------------------------------------------
+def _clip_store(bank, start, cap_or_n, second):
+    """the checks both launches share: a 16-byte aligned fp32 bank of a multiple of 4 floats, int64 starts, one int32 per clip"""
+    _chk(bank, 'bank'); _chk(start, 'start', torch.int64); _chk(cap_or_n, second, torch.int32)
+    if bank.dim() != 1 or not bank.is_contiguous() or bank.numel() % 4 or bank.data_ptr() % 16:
+        raise ValueError('audiogan_amd: the clip bank must be 1-D, contiguous, 16-byte aligned and a multiple of 4 floats long')
+    nc = start.numel()
+    if start.dim() != 1 or not start.is_contiguous() or tuple(cap_or_n.shape) != (nc,) or not cap_or_n.is_contiguous():
+        raise ValueError('audiogan_amd: start and %s must be contiguous vectors with one entry per clip' % second)
+    return nc
+
+
+def clip_facts(bank, start, cap):
+    """the packed store ``bank`` (fp32, clip c = bank[start[c] : start[c] + cap[c]], every start a multiple of 4 floats;
+    ``start`` int64, ``cap`` int32) -> (n int32 [n_clips], peak fp32 [n_clips]): n = the index after the last sample that
+    is not +-0 (a denormal and a NaN count), peak = max |x|, a NaN if the clip holds one, +inf for an infinite sample.
+    Exact (ag_clip_facts: one launch, one workgroup per clip)."""
+    nc = _clip_store(bank, start, cap, 'cap')
+    n = torch.empty(nc, dtype=torch.int32, device=bank.device)
+    peak = torch.empty(nc, dtype=torch.float32, device=bank.device)
+    check(lib.ag_clip_facts(_p(bank), _p(start), _p(cap), _p(n), _p(peak), nc, _stream()), 'ag_clip_facts')
+    return n, peak
+
+
+def clip_gather(bank, start, n, peak, ids, out, len_out=None, frame=0):
+    """``ids`` int64 [B] on the device, every one a clip of the store (the CALLER's duty: ``dataset.ClipBatch`` checks them on
+    the host); ``out`` fp32 [B, W], unit stride along W, any row pitch and alignment; ``len_out`` int64 [B] or None.
+    out[b, t] = bank[start[c] + t] / peak[c] for t < min(n[c], W), c = ids[b], else 0 - the division correctly rounded, the
+    bits of the host loader's float64 divide and float32 cast; len_out[b] = n[c] rounded up to ``frame`` (0: n[c]), not
+    cropped to W (ag_clip_gather: one launch).  -> (out, len_out)"""
+    nc = _clip_store(bank, start, n, 'n')
+    _chk(peak, 'peak'); _chk(ids, 'ids', torch.int64); _chk(len_out, 'len_out', torch.int64)
+    if tuple(peak.shape) != (nc,) or not peak.is_contiguous() or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError('audiogan_amd: peak must be a contiguous vector with one entry per clip, ids a contiguous vector')
+    B = ids.numel()
+    _chk(out, 'out')
+    if out.dim() != 2 or out.size(0) != B or (out.size(1) > 1 and out.stride(1) != 1):
+        raise ValueError('audiogan_amd: out must be [%d, W] with unit stride along W, got %r with strides %r'
+                         % (B, tuple(out.shape), out.stride()))
+    if len_out is not None and (tuple(len_out.shape) != (B,) or not len_out.is_contiguous()):
+        raise ValueError('audiogan_amd: len_out must be a contiguous vector of %d entries' % B)
+    W = out.size(1)
+    ld = out.stride(0) if B > 1 else max(out.stride(0), W)
+    check(lib.ag_clip_gather(_p(bank), _p(start), _p(n), _p(peak), _p(ids), B, _p(out), ld, W, _p(len_out), int(frame or 0),
+                             _stream()), 'ag_clip_gather')
+    return out, len_out
+
+
+for _n in ('clip_facts', 'clip_gather'):
+    _instrument(_n, _work_named)

@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, train
+from .dataset import ClipBatch
 
 
 class TrainLoop(object):
@@ -53,7 +54,8 @@ class TrainLoop(object):
                  host=None, sample_every=0, sample_words=None, sample_z=None, sample_seed=0, on_sample=None, sample_dir=None,
                  audio_every=500, summary=None, summary_every=None, ema=None, sample_ema=True, evaluator=None, eval_every=0):
         """``loader``: the generator ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths, keys, cseq,
-        clen], dataset.py:91); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
+        clen], dataset.py:91; ``samples`` may be a ``dataset.ClipBatch`` - ``dataset.device_dataloader`` - which is then gathered
+        on the device straight into the iteration's input, the same bits as the host array's); ``pick_words``: a callable () -> (cseq, clen) numpy arrays for ``batch_size`` random words
         (``dataset.pick_words(..., skip_samples=True)[1:3]``, audiogan.py:715-716); ``stop``: None = Bernoulli stop draws
         like the reference (a host sync per generator forward), 'never' = fixed-length clips.  ``opt_d`` holds the parameters
         of d and e_d, ``opt_g`` those of g and e_g (:690-691).
@@ -103,6 +105,7 @@ class TrainLoop(object):
         # captured iterations do; an eager loop with host=False runs the very same arithmetic (tests compare the two bit for bit)
         self.host = (not self.graphed) if host is None else bool(host)
         self._graphs = None
+        self._clips = False          # the loader yields dataset.ClipBatch (dataset.device_dataloader): set at the first minibatch
         # host milliseconds spent per phase of the captured iterations (enqueueing a replay, the loader, staging the upload,
         # feeding the static inputs), summed since construction: bench.py --workload full reports them per pass
         self.host_ms = dict(replay=0.0, loader=0.0, stage=0.0, inputs=0.0)
@@ -134,6 +137,11 @@ class TrainLoop(object):
     def _real(self):
         """``tovar`` of the loader's next minibatch (audiogan.py:94-97, :714): float32 clips padded to the frame grid"""
         _, _, samples, lengths, _, cseq, clen = next(self.loader)
+        if isinstance(samples, ClipBatch):          # a device-resident word store: one launch writes rows and lengths
+            self._clips = True
+            real, real_len = samples.gather(torch.empty(self.B, self.L, device=self.dev),
+                                            torch.empty(self.B, dtype=torch.long, device=self.dev))
+            return real, real_len, self._up(cseq, torch.long), self._up(clen, torch.long)
         x = np.zeros((self.B, self.L), dtype=np.float32)
         n = min(self.L, samples.shape[1])
         x[:, :n] = samples[:, :n]
@@ -180,7 +188,9 @@ class TrainLoop(object):
                   (self.baseline.detach().clone().float().reshape(()) if torch.is_tensor(self.baseline) else
                    torch.as_tensor(float(self.baseline), device=dev, dtype=torch.float32)))
         self._static, self._out = st, {}
-        self._feeder = train.Feeder(st, keys=['real', 'real_len', 'lcs', 'lcl', 'wcs', 'wcl'])
+        # (the warm-up saw what the loader yields: with a device-resident store only the clip ids are staged)
+        self._feeder = train.Feeder(st, keys=['real', 'real_len', 'lcs', 'lcl', 'wcs', 'wcl'],
+                                    **(dict(clips=('real', 'real_len')) if self._clips else {}))
         K.reserve_table_arena()
         mark = K.capture_mark()
 
@@ -222,11 +232,14 @@ class TrainLoop(object):
         """what every iteration takes from the host, in the order the eager iterations draw it: the loader's next minibatch
         (:714) and one pick_words batch (:715-716), at the static shapes / dtypes"""
         _, _, samples, lengths, _, cseq, clen = next(self.loader)
+        i64 = lambda v: np.ascontiguousarray(np.asarray(v), dtype=np.int64)   # noqa: E731
+        if isinstance(samples, ClipBatch):          # (the Feeder was built with clips=: it stages the ids and gathers at feed())
+            ws, wl = self.pick_words()
+            return dict(real=samples, lcs=i64(cseq), lcl=i64(clen), wcs=i64(ws), wcl=i64(wl))
         x = np.zeros((self.B, self.L), dtype=np.float32)
         n = min(self.L, samples.shape[1])
         x[:, :n] = samples[:, :n]
         ws, wl = self.pick_words()
-        i64 = lambda v: np.ascontiguousarray(np.asarray(v), dtype=np.int64)   # noqa: E731
         return dict(real=x, real_len=i64(lengths), lcs=i64(cseq), lcl=i64(clen), wcs=i64(ws), wcl=i64(wl))
 
     def _next_inputs(self, noises):

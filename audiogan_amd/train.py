@@ -533,18 +533,28 @@ def batch_from_loader(item, device_noise=True):
 
 
 class Feeder(object):
-    def __init__(self, static, keys=None, device_fill=None):
+    def __init__(self, static, keys=None, device_fill=None, clips=None):
         """``static``: dict of the step's static device tensors (``GraphedStep.b``).  ``keys``: the entries that come
         from the host (default: all of ``static``); the others stay as they are unless ``device_fill`` (dict key ->
         callable(tensor), e.g. ``lambda t: t.normal_().mul_(0.01)`` for instance noise / z) refreshes them on the device
-        at every step boundary."""
+        at every step boundary.  ``clips=(real_key, len_key)``: the host batch carries a ``dataset.ClipBatch`` under
+        ``real_key`` (a device-resident word store); those two tensors are not staged - only the batch's clip ids are, B
+        int64 values - and ``feed()`` enqueues one ``ClipBatch.gather`` into ``static[real_key]`` / ``static[len_key]``."""
         self.static = static
         self.keys = list(keys) if keys is not None else list(static.keys())
         self.device_fill = dict(device_fill or {})
-        for k in self.keys + list(self.device_fill):
+        self.clips = tuple(clips) if clips is not None else None
+        for k in self.keys + list(self.device_fill) + list(self.clips or ()):
             if k not in static:
                 raise KeyError('Feeder: %r is not one of the step\'s static tensors %r' % (k, sorted(static)))
-        any_t = static[self.keys[0]]
+        any_t = static[(self.keys + list(self.clips or ()))[0]]
+        if self.clips is not None:
+            self.keys = [k for k in self.keys if k not in self.clips]
+            B = static[self.clips[0]].size(0)
+            pin = any_t.is_cuda
+            self._ids_pin = [torch.empty(B, dtype=torch.int64, pin_memory=pin) for _ in range(2)]
+            self._ids_dev = [torch.empty(B, dtype=torch.int64, device=any_t.device) for _ in range(2)]
+            self._batch = [None, None]
         self.cuda = any_t.is_cuda
         self.n_staged = self.n_fed = 0
         self.host_ms = dict(sync=0.0, pin=0.0, sync_max=0.0, pin_max=0.0)     # where stage() spends host time
@@ -572,6 +582,21 @@ class Feeder(object):
                 raise TypeError('Feeder.stage: %r is %s, expected %s' % (k, t.dtype, self.static[k].dtype))
             yield k, t
 
+    def _check_clips(self, host):
+        from .dataset import ClipBatch
+        real_key = self.clips[0]
+        batch = host.get(real_key) if hasattr(host, 'get') else None
+        if not isinstance(batch, ClipBatch):
+            raise TypeError('Feeder.stage: with clips=%r the host batch carries a dataset.ClipBatch under %r, got %s'
+                            % (self.clips, real_key, type(batch).__name__))
+        B = self.static[real_key].size(0)
+        if len(batch) != B:
+            raise ValueError('Feeder.stage: a ClipBatch of %d clips, the captured step expects %d' % (len(batch), B))
+        if batch.store.bank.device != self.static[real_key].device:
+            raise ValueError('Feeder.stage: the ClipBatch\'s store is on %s, the step\'s tensors on %s'
+                             % (batch.store.bank.device, self.static[real_key].device))
+        return batch
+
     def stage(self, host):
         """start moving the NEXT minibatch (dict key -> numpy array / CPU tensor) towards the device; returns at once.
         At most one batch can be staged ahead of the one being fed."""
@@ -579,9 +604,12 @@ class Feeder(object):
             raise RuntimeError('Feeder.stage: two minibatches are already staged; call feed() first')
         slot = self.n_staged & 1
         items = list(self._check(host))
+        batch = self._check_clips(host) if self.clips is not None else None
         if not self.cuda:
             for k, t in items:
                 self.dev[slot][k].copy_(t)
+            if batch is not None:
+                self._ids_dev[slot].copy_(torch.from_numpy(batch.ids))
         else:
             import time as _t
             t0 = _t.perf_counter()
@@ -593,6 +621,8 @@ class Feeder(object):
             # process throttled for the rest of the scheduler period - 90 ms stalls once per pass were measured)
             for k, t in items:
                 self.pinned_np[slot][k][...] = t.numpy()
+            if batch is not None:
+                self._ids_pin[slot].numpy()[...] = batch.ids
             t2 = _t.perf_counter()
             self.host_ms['sync'] += (t1 - t0) * 1e3; self.host_ms['pin'] += (t2 - t1) * 1e3
             self.host_ms['sync_max'] = max(self.host_ms['sync_max'], (t1 - t0) * 1e3)
@@ -602,9 +632,13 @@ class Feeder(object):
                     self.copy_stream.wait_event(self._free[slot])
                 for k, _ in items:
                     self.dev[slot][k].copy_(self.pinned[slot][k], non_blocking=True)
+                if batch is not None:
+                    self._ids_dev[slot].copy_(self._ids_pin[slot], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
                 self._ready[slot] = ev
+        if batch is not None:
+            self._batch[slot] = batch
         self.n_staged += 1
 
     def feed(self):
@@ -617,6 +651,8 @@ class Feeder(object):
             torch.cuda.current_stream().wait_event(self._ready[slot])
         for k in self.keys:
             self.static[k].copy_(self.dev[slot][k], non_blocking=True)
+        if self.clips is not None:
+            self._batch[slot].gather(self.static[self.clips[0]], self.static[self.clips[1]], ids=self._ids_dev[slot])
         if self.cuda:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())

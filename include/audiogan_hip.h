@@ -848,6 +848,36 @@ int ag_resample_poly(const void* src, int src_kind, int channels, long long src_
                      long long n_in, long long in_start, const float* bank, int L, int M, int taps, float* dst,
                      long long dst_pitch, long long n_out, long long out_start, int B, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ag_clip_facts, ag_clip_gather (csrc/clipstore.hip): the loader's minibatch assembled on the device from a packed store of
+ * every clip (dataset.DeviceWordStore, dataset.ClipBatch).  They stand where the reference's pick_word scans, normalises
+ * and stacks float64 rows on the host at every draw (dataset.py:48-77).  fp32 whatever ag_set_precision says; no atomics,
+ * no workspace, one launch each.
+ *   The packed store (laid out by the Python side, relied on here): clip c is bank[start[c] : start[c] + cap[c]] (fp32);
+ *   start int64 - the bank may exceed 2^31 floats - and every start[c] a multiple of 4 floats; cap int32.  bank is 16-byte
+ *   aligned, its allocation a multiple of 4 floats, so a 16-byte load at t % 4 == 0, t < cap[c] never leaves it.
+ *   ag_clip_facts   per clip c < n_clips: n_out[c] (int32) = the index after the last sample whose bits are not those of
+ *                   +0.0 or -0.0 (a denormal and a NaN are not zero), 0 if there is none - the loader's length rule
+ *                   (dataset.py:52); peak_out[c] = max |x| over the clip, +inf for an infinite sample and a NaN if any
+ *                   sample is one (formed as the largest |x| bit pattern, so no flushed or dropped value takes part).
+ *                   Both are order-independent: exact.  One workgroup per clip.                        "clip_facts_kernel"
+ *   ag_clip_gather  for b < B, t < L_out, c = ids[b] (int64 on the device, 0 <= c < n_clips: the CALLER's duty):
+ *                     out[b * ld_out + t] = t < min(n[c], L_out) ? bank[start[c] + t] / peak[c] : 0
+ *                   the division correctly rounded in fp32 (= the host's float64 divide followed by the float32 cast);
+ *                     len_out[b] (int64, may be NULL) = frame > 0 ? roundup(n[c], frame) : n[c], not cropped to L_out.
+ *                   Nothing outside [0, L_out) of a row is written.  Grid (ceil(L_out / 1024), B), four consecutive
+ *                   samples per thread with 16-byte loads and stores when out is 16-byte aligned and ld_out % 4 == 0
+ *                   (the last, partial group of a row with scalar stores), one sample per access otherwise.
+ *                                                                       "clip_gather_kernel<1>" (16-byte) / "<0>" (scalar)
+ *   Refused from host code before any HIP call (AG_ERR_ARG): a negative n_clips, B, L_out or frame; B above 65535; a null
+ *   or misaligned bank, a null start, cap, n, peak, ids or out with work to do; ld_out < L_out.  n_clips = 0, or B = 0:
+ *   AG_OK with no launch.
+ * ------------------------------------------------------------------------- */
+int ag_clip_facts(const float* bank, const long long* start, const int32_t* cap, int32_t* n_out, float* peak_out,
+                  long long n_clips, void* stream);
+int ag_clip_gather(const float* bank, const long long* start, const int32_t* n, const float* peak, const long long* ids,
+                   int B, float* out, long long ld_out, int L_out, long long* len_out, int frame, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
