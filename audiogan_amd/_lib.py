@@ -192,6 +192,12 @@ SIGNATURES = {
                                    C.c_int, vp]),
     'ag_clip_facts': (C.c_int, [vp, vp, vp, vp, vp, i64, vp]),
     'ag_clip_gather': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp, C.c_int, vp]),
+    'ag_frame_power_ok': (C.c_int, [C.c_int] * 2),
+    'ag_frame_power_tile': (C.c_int, [C.c_int] * 2),
+    'ag_frame_power': (C.c_int, [vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, i64, i64, i64, C.c_int, vp]),
+    'ag_activity_chunk': (C.c_int, []),
+    'ag_activity_segments': (C.c_int, [vp, i64, vp, C.c_int, vp, f32, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                       C.c_int, vp, vp, C.c_int, vp]),
 }
 
 
@@ -200,6 +206,9 @@ def _load():
         raise ImportError(
             'audiogan_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; '
             'g.build()"` or `make -C audiogan_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
+    # torch first: it ships a HIP runtime of its own, and the process must take that one before this library's loader looks
+    # for one - the other way round the library's launches find no device (`python -m audiogan_amd.ingest --device cuda`)
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing

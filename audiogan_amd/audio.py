@@ -7,7 +7,12 @@ In: what the reference's preprocessing reads with ``librosa.load(wav, sr=8000)``
 preprocess-fisher.py:232): ``read_wav`` (RIFF WAV, standard library and numpy), and a polyphase windowed-sinc resampler to
 the models' 8 kHz - ``resample_bank`` designs the filter bank on the host in float64, ``resample64`` is the rule in float64
 numpy (the path without a GPU, and the reference of every test), ``resample`` runs it on the device through
-``kernels.resample_poly`` (ag_resample_poly), in chunks."""
+``kernels.resample_poly`` (ag_resample_poly), in chunks.
+
+Where the words are: ``activity`` finds the active stretches of rows of 8 kHz samples by short-time energy (the reference cuts
+words by a forced alignment, preprocess-fisher.py:145-146, or keeps loud windows, preprocess.py:25-27) - ``activity_rule`` is
+the rule on the host, ``activity64`` the path without a GPU, and on the device ``kernels.frame_power`` and
+``kernels.activity_segments`` (ag_frame_power, ag_activity_segments) run it."""
 import math
 import struct
 import warnings
@@ -275,3 +280,174 @@ def resample(x, sr_in, sr_out=8000, lens=None, device=None, chunk=1 << 22):
         if ln[b]:
             y[b, :counts[b]] = resample64(xh[b, :ln[b]], sr_in, sr_out)
     return torch.from_numpy(y).to(device), counts
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# activity: an energy gate relative to the loudest frame (the rule of include/audiogan_hip.h: ag_activity_segments)
+# ------------------------------------------------------------------------------------------------------------------
+def activity_params(sr=8000, top_db=40.0, floor_db=-80.0, win_ms=25.0, hop_ms=10.0, min_gap_ms=300.0, min_run_ms=50.0,
+                    pad_ms=30.0):
+    """the options of ``activity`` as the launches take them: win = round(sr win_ms / 1000), hop likewise, the three durations
+    in frames as ceil(ms / hop_ms), ratio = fp32(10^(-top_db / 10)), floor = fp32(10^(floor_db / 10))"""
+    win, hop = int(round(sr * win_ms / 1000.0)), int(round(sr * hop_ms / 1000.0))
+    if not 1 <= hop <= win <= 4096:
+        raise ValueError('audiogan_amd: a window of %d samples at a hop of %d: 1 <= hop <= win <= 4096' % (win, hop))
+    frames = lambda ms: int(math.ceil(ms / float(hop_ms)))          # noqa: E731
+    return dict(win=win, hop=hop, min_gap=frames(min_gap_ms), min_run=frames(min_run_ms), pad=frames(pad_ms),
+                ratio=np.float32(10.0 ** (-top_db / 10.0)), floor=np.float32(10.0 ** (floor_db / 10.0)))
+
+
+def frame_count(n, hop):
+    """frames of a row of ``n`` samples: ceil(n / hop) - every frame that starts inside the row; the last ones run past its
+    end and read zeros there, so a word at the very end of a file is still seen"""
+    return (np.asarray(n, dtype=np.int64) + hop - 1) // hop
+
+
+def _order_keys(p):
+    """fp32 -> int32 in the order of the values, -0 below +0 (its own inverse on the bits)"""
+    i = np.ascontiguousarray(p, dtype=np.float32).view(np.int32)
+    return i ^ ((i >> 31) & np.int32(0x7fffffff))
+
+
+def activity_rule(power, nf, lens, ratio, floor, min_gap, min_run, pad, win, hop):
+    """THE RULE on the host, run by run.  ``power`` [B, F] fp32, ``nf`` [B] frames and ``lens`` [B] samples per row ->
+    (segs, count int32 [B], pmax fp32 [B]); segs[b] is an int64 array [count, 2] of (start, end) samples, None for a row with
+    a NaN or an infinity (count -1, pmax NaN).  All in integers but for thr = max(fp32(pmax ratio), floor):
+      1. active[f] = power[f] > thr, pmax the row's largest power (0 for an empty row);
+      2. an inactive run strictly between two active frames and shorter than ``min_gap`` becomes active;
+      3. then an active run shorter than ``min_run`` becomes inactive;
+      4. a run of frames [a, b) becomes samples [max(0, (a - pad) hop), min(len, (b - 1 + pad) hop + win)); ranges that overlap
+         or touch become one."""
+    power = np.asarray(power, dtype=np.float32)
+    power = power.reshape(1, -1) if power.ndim == 1 else power
+    B, F = power.shape
+    nf = np.clip(np.asarray(nf, dtype=np.int64).reshape(B), 0, F)
+    lens = np.maximum(np.asarray(lens, dtype=np.int64).reshape(B), 0)
+    ratio, floor = np.float32(ratio), np.float32(floor)
+    segs, count, pmax = [], np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
+    for b in range(B):
+        p = power[b, :nf[b]]
+        if not np.isfinite(p).all():
+            segs.append(None)
+            count[b], pmax[b] = -1, np.float32(np.nan)
+            continue
+        out = []
+        if len(p):
+            key = np.array([_order_keys(p).max()], dtype=np.int32)
+            pmax[b] = _order_keys(key.view(np.float32)).view(np.float32)[0]
+            with np.errstate(over='ignore', under='ignore'):
+                thr = np.maximum(np.float32(pmax[b] * ratio), floor)
+            flag = np.concatenate([[0], (p > thr).astype(np.int8), [0]])
+            flips = np.flatnonzero(np.diff(flag))          # starts and ends of the raw runs, in turn
+            closed = []
+            for a, e in zip(flips[0::2].tolist(), flips[1::2].tolist()):
+                if closed and a - closed[-1][1] < min_gap:
+                    closed[-1][1] = e
+                else:
+                    closed.append([a, e])
+            for a, e in closed:
+                if e - a < min_run:
+                    continue
+                s0, s1 = max(0, (a - pad) * hop), min(int(lens[b]), (e - 1 + pad) * hop + win)
+                if out and s0 <= out[-1][1]:
+                    out[-1][1] = max(out[-1][1], s1)
+                else:
+                    out.append([s0, s1])
+        segs.append(np.array(out, dtype=np.int64).reshape(-1, 2))
+        count[b] = len(out)
+    return segs, count, pmax
+
+
+def frame_power64(x, n, win, hop, n_frames=None):
+    """float64: the mean of x^2 over samples f hop .. f hop + win - 1 of ``x[:n]`` (zero past n) for f < n_frames (default
+    ceil(n / hop)) - a cumulative sum of squares would cancel, so frames are summed one by one, vectorised over the frames"""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)[:int(n)]
+    if n_frames is None:
+        n_frames = int(frame_count(len(x), hop))
+    sq = np.zeros(max(0, (n_frames - 1) * hop + win), dtype=np.float64)
+    m = min(len(sq), len(x))
+    sq[:m] = x[:m] ** 2
+    if n_frames == 0:
+        return np.zeros(0, dtype=np.float64)
+    rows = np.lib.stride_tricks.as_strided(sq, shape=(n_frames, win), strides=(hop * sq.strides[0], sq.strides[0]), writeable=False)
+    return rows.sum(1) / float(win)
+
+
+def _rows_and_lens(y, lens):
+    is_t = hasattr(y, 'detach')
+    if not is_t:
+        y = np.asarray(y)
+    nd = y.dim() if is_t else y.ndim
+    if nd == 1:
+        y = y[None, :]
+    elif nd != 2:
+        raise ValueError('audiogan_amd: activity takes [n] or [B, n], got %d axes' % nd)
+    B, n = int(y.shape[0]), int(y.shape[1])
+    ln = np.full(B, n, dtype=np.int64) if lens is None else np.clip(
+        (lens.detach().cpu().numpy() if hasattr(lens, 'detach') else np.asarray(lens)).astype(np.int64).reshape(B), 0, n)
+    return y, is_t, B, n, ln
+
+
+def activity64(y, lens=None, sr=8000, **options):
+    """the path without a GPU: the frame power in float64 numpy (``frame_power64``), rounded once to fp32, then
+    ``activity_rule``.  Options and result as ``activity``."""
+    y, is_t, B, n, ln = _rows_and_lens(y, lens)
+    yh = y.detach().cpu().numpy() if is_t else y
+    q = activity_params(sr, **options)
+    nf = frame_count(ln, q['hop'])
+    power = np.zeros((B, int(nf.max()) if B else 0), dtype=np.float32)
+    for b in range(B):
+        power[b, :nf[b]] = frame_power64(yh[b], ln[b], q['win'], q['hop']).astype(np.float32)
+    return activity_rule(power, nf, ln, q['ratio'], q['floor'], q['min_gap'], q['min_run'], q['pad'], q['win'], q['hop'])[0]
+
+
+def activity(y, lens=None, sr=8000, top_db=40.0, floor_db=-80.0, win_ms=25.0, hop_ms=10.0, min_gap_ms=300.0, min_run_ms=50.0,
+             pad_ms=30.0, device=None, chunk=1 << 22, max_segments=256):
+    """where the rows are active.  ``y`` [n] or [B, n], numpy or tensor, at ``sr`` Hz; ``lens``: samples per row (default n) ->
+    a list with one int64 array [count, 2] of (start, end) samples per row, None for a row that holds a NaN or an infinity.
+
+    A frame of ``win_ms`` every ``hop_ms`` (a row of n samples has ceil(n / hop) of them, the last ones zero-filled) is active
+    when its mean power exceeds max(the row's largest / 10^(top_db / 10), 10^(floor_db / 10)).  Pauses shorter than
+    ``min_gap_ms`` inside a stretch are closed, then stretches shorter than ``min_run_ms`` dropped, then ``pad_ms`` added either
+    side and stretches that meet merged (``activity_rule``).  An energy gate relative to the loudest frame, as
+    librosa.effects.trim / split are - not a speech detector: music or a slammed door pass it.
+
+    On a CUDA device two launches: ``kernels.frame_power`` (one launch for a device tensor; a host source is uploaded in
+    windows of ``chunk`` samples with the two starts set, which gives the bits of one launch) and
+    ``kernels.activity_segments`` with K = ``max_segments``, run once more with K = the largest count when a row has more.
+    Without a GPU ``activity64``: the power in float64 rounded once to fp32, the same integer rule.  The two paths can differ
+    only where a frame's power lies within fp32 rounding of the threshold (or of the largest frame's, which sets it)."""
+    import torch
+    y, is_t, B, n, ln = _rows_and_lens(y, lens)
+    if device is None:
+        device = y.device if is_t and y.is_cuda else ('cuda' if torch.cuda.is_available() else 'cpu')
+    device = torch.device(device)
+    options = dict(top_db=top_db, floor_db=floor_db, win_ms=win_ms, hop_ms=hop_ms, min_gap_ms=min_gap_ms,
+                   min_run_ms=min_run_ms, pad_ms=pad_ms)
+    if device.type != 'cuda':
+        return activity64(y, ln, sr, **options)
+    from . import kernels as K
+    q = activity_params(sr, **options)
+    win, hop = q['win'], q['hop']
+    nf = frame_count(ln, hop)
+    F = int(nf.max()) if B else 0
+    ln_t = torch.from_numpy(ln)
+    power = torch.empty(B, F, dtype=torch.float32, device=device)
+    if is_t and y.is_cuda:
+        K.frame_power(y.float(), ln_t.to(device), win, hop, dst=power)
+    else:
+        per = max(1, (max(1, int(chunk)) - win) // hop + 1)          # frames whose samples fit one window
+        for f0 in range(0, F, per):
+            f1 = min(F, f0 + per)
+            lo, hi = f0 * hop, min(n, (f1 - 1) * hop + win)
+            part = y[:, lo:hi]
+            part = part.float().to(device) if is_t else torch.from_numpy(np.ascontiguousarray(part, dtype=np.float32)).to(device)
+            K.frame_power(part, (ln_t - lo).clamp_(0, hi - lo).to(device), win, hop, dst=power[:, f0:f1], in_start=lo, f_start=f0)
+    args = (power, torch.from_numpy(nf.astype(np.int32)).to(device), ln_t.to(device), q['ratio'], q['floor'], q['min_gap'],
+            q['min_run'], q['pad'], win, hop)
+    seg, count, _ = K.activity_segments(*args, K=max(0, int(max_segments)))
+    count = count.cpu().numpy()
+    if B and int(count.max()) > seg.size(1):
+        seg, _, _ = K.activity_segments(*args, K=int(count.max()))
+    seg = seg.cpu().numpy()
+    return [None if count[b] < 0 else seg[b, :count[b]].copy() for b in range(B)]

@@ -2243,3 +2243,70 @@ def clip_gather(bank, start, n, peak, ids, out, len_out=None, frame=0):
 
 for _n in ('clip_facts', 'clip_gather'):
     _instrument(_n, _work_named)
+
+
+# ------------------------------------------------------------------------------------
+# activity detection (audio.activity, ingest.build_store(trim / split)): frame power of ragged rows, runs of active frames
+# ------------------------------------------------------------------------------------
+FRAME_POWER_TILE_MAX = 256                                # frames: the largest tile of ag_frame_power
+ACTIVITY_CHUNK = int(lib.ag_activity_chunk())             # frames ag_activity_segments walks at a time
+
+
+def frame_power_ok(win, hop):
+    """the library's rule for ag_frame_power and ag_activity_segments: 1 <= hop <= win <= 4096"""
+    return bool(lib.ag_frame_power_ok(int(win), int(hop)))
+
+
+def frame_power_tile(win, hop):
+    """frames one workgroup of ag_frame_power takes at (win, hop): the most, up to 256, whose samples fit 64 KB of LDS"""
+    return int(lib.ag_frame_power_tile(int(win), int(hop)))
+
+
+def frame_power(src, src_len, win, hop, dst=None, n_frames=None, in_start=0, f_start=0):
+    """src [B, n_in] fp32 (unit stride along the samples, any row pitch and alignment): samples in_start .. in_start + len_b - 1
+    of B signals, len_b = clamp(src_len[b], 0, n_in) (int64 [B] or None: n_in), zero elsewhere.  -> dst [B, n_frames] fp32:
+    dst[b, j] = the mean of x^2 over samples f hop .. f hop + win - 1, f = f_start + j, in the fixed order of the header (block
+    sums over gcd(win, hop) samples, then a chain per frame).  ``n_frames`` defaults to ceil(n_in / hop); ALL n_frames entries
+    of every row are written.  A chunk of a signal (its two starts set) has the bits of the whole (ag_frame_power: one
+    launch)."""
+    _chk(src, 'src'); _chk(src_len, 'src_len', torch.int64)
+    assert src.dim() == 2 and (src.size(1) <= 1 or src.stride(1) == 1), (tuple(src.shape), src.stride())
+    B, n_in = src.size(0), src.size(1)
+    pitch = src.stride(0) if B > 1 else max(src.stride(0), n_in)
+    assert src_len is None or (src_len.is_contiguous() and src_len.numel() == B)
+    if n_frames is None:
+        n_frames = dst.size(1) if dst is not None else (n_in + int(hop) - 1) // int(hop)
+    if dst is None:
+        dst = torch.empty(B, n_frames, dtype=torch.float32, device=src.device)
+    ldd = _rows(dst, 'dst', B, n_frames)
+    check(lib.ag_frame_power(_p(src), pitch, _p(src_len), n_in, int(in_start), int(win), int(hop), _p(dst), ldd, int(f_start),
+                             n_frames, B, _stream()), 'ag_frame_power')
+    return dst
+
+
+def activity_segments(power, nf, lens, ratio, floor, min_gap, min_run, pad, win, hop, K=256, seg=None):
+    """power [B, F] fp32 (unit stride along F, any row pitch), nf int32 [B] (<= F), lens int64 [B] -> (seg int64 [B, K, 2],
+    count int32 [B], pmax fp32 [B]): the rule of the header - threshold max(pmax ratio, floor), gaps shorter than ``min_gap``
+    frames closed, runs shorter than ``min_run`` frames dropped, ``pad`` frames added either side, overlapping or touching
+    sample ranges merged.  count is the number of runs even above K; seg[b, k] is written for k < min(count, K) only (a ``seg``
+    that is given keeps its other entries; a fresh one holds -1 there).  count = -1: a NaN or an infinity in the row
+    (ag_activity_segments: one launch)."""
+    _chk(power, 'power'); _chk(nf, 'nf', torch.int32); _chk(lens, 'lens', torch.int64); _chk(seg, 'seg', torch.int64)
+    assert power.dim() == 2 and (power.size(1) <= 1 or power.stride(1) == 1), (tuple(power.shape), power.stride())
+    B, F = power.size(0), power.size(1)
+    pitch = power.stride(0) if B > 1 else max(power.stride(0), F)
+    assert nf.is_contiguous() and nf.numel() == B and lens.is_contiguous() and lens.numel() == B
+    K = int(K)
+    if seg is None:
+        seg = torch.full((B, max(K, 0), 2), -1, dtype=torch.int64, device=power.device)
+    assert seg.is_contiguous() and tuple(seg.shape) == (B, K, 2), (tuple(seg.shape), (B, K, 2))
+    count = torch.empty(B, dtype=torch.int32, device=power.device)
+    pmax = torch.empty(B, dtype=torch.float32, device=power.device)
+    check(lib.ag_activity_segments(_p(power), pitch, _p(nf), F, _p(lens), float(ratio), float(floor), int(min_gap), int(min_run),
+                                   int(pad), int(win), int(hop), _p(seg), K, _p(count), _p(pmax), B, _stream()),
+          'ag_activity_segments')
+    return seg, count, pmax
+
+
+for _n in ('frame_power', 'activity_segments'):
+    _instrument(_n, _work_named)

@@ -878,6 +878,61 @@ int ag_clip_facts(const float* bank, const long long* start, const int32_t* cap,
 int ag_clip_gather(const float* bank, const long long* start, const int32_t* n, const float* peak, const long long* ids,
                    int B, float* out, long long ld_out, int L_out, long long* len_out, int frame, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ag_frame_power, ag_activity_segments (csrc/activity.hip): short-time energy activity detection on the resampled rows
+ * (audio.activity, ingest.build_store(trim / split)).  They stand where the reference's preprocessing cuts words by a forced
+ * alignment (preprocess-fisher.py:145-146) or keeps windows by an amplitude threshold (preprocess.py:25-27).  fp32 whatever
+ * ag_set_precision says; no atomics, no workspace, one launch each.
+ *   ag_frame_power
+ *     src        B rows of fp32 samples, src_pitch ELEMENTS apart, 4-byte aligned.  Row b holds samples in_start .. in_start +
+ *                len_b - 1 of its signal (absolute sample indices), len_b = clamp(src_len[b], 0, n_in) (int64 on the device;
+ *                NULL: n_in).  Every other sample reads as zero and is never loaded.
+ *     dst[b, j]  j < n_frames, rows dst_pitch floats apart, = the power of frame f = f_start + j: the sum of x^2 over samples
+ *                f hop .. f hop + win - 1 times fp32(1 / win), f hop in 64 bits.  ALL n_frames entries of every row are written.
+ *     THE ORDER  with g = gcd(win, hop), hq = hop / g, wq = win / g the signal falls into blocks of g samples that start at
+ *                multiples of g of the absolute sample index;
+ *                  S_k = the fmaf chain s = fmaf(x, x, s) over samples k g .. k g + g - 1 ascending, from s = 0;
+ *                  P_f = ((0 + S_{f hq}) + S_{f hq + 1}) + .. + S_{f hq + wq - 1};   dst = P_f * (1.0f / win).
+ *                That is the whole of a frame's arithmetic, whatever b, j, the tile, in_start or f_start: a signal processed
+ *                in chunks (a row holding just the samples its frames read, with the two starts set) has the bits of the
+ *                same signal processed at once.
+ *     One workgroup per (row, tile of ag_frame_power_tile(win, hop) <= 256 frames): the tile's samples are staged once into
+ *     LDS (16-byte loads at aligned addresses, whatever the row's own alignment) at an odd block pitch, thread k forms block
+ *     sum k, thread j frame j.                                                                       "frame_power_kernel"
+ *     ag_frame_power_ok: 1 when 1 <= hop <= win <= 4096.  ag_frame_power_tile: the launch's tile of frames (0 when refused).
+ *     Refused from host code before any HIP call (AG_ERR_ARG): anything the predicate refuses; a negative size, start or B;
+ *     a null dst, or a null src with n_in > 0, with work to do; src not 4-byte aligned; src_pitch < n_in; dst_pitch <
+ *     n_frames; f_start or n_frames past 2^40; more than 2^31 - 1 tiles in one launch.  B = 0 or n_frames = 0: AG_OK, no launch.
+ *   ag_activity_segments
+ *     power [B, F] fp32, rows power_pitch floats apart; nf[b] (int32, clamped to 0 .. F) frames of row b; len[b] (int64,
+ *     clamped at 0) its samples; seg [B, K, 2] int64; count [B] int32; pmax [B] fp32.  Per row, in integers but for the two
+ *     fp32 operations named:
+ *       1. pmax = max_f power[f] (order-free: exact; -0 counts below +0);  thr = max(pmax * ratio, floor): one fp32 multiply,
+ *          one max;  active[f] = power[f] > thr.
+ *       2. close: an inactive run strictly between two active frames and shorter than min_gap frames becomes active.
+ *       3. drop: after closing, an active run shorter than min_run frames becomes inactive.
+ *       4. pad and merge: a run of frames [a, b) becomes samples [max(0, (a - pad) hop), min(len, (b - 1 + pad) hop + win));
+ *          runs whose sample ranges overlap or touch become one.
+ *       5. count[b] = the number of runs left, even above K; seg[b, k] = (start, end) for k < min(count, K), ascending;
+ *          entries past that are NOT written.
+ *       6. nf = 0 or no active frame: count = 0 (pmax = 0 for nf = 0).  A NaN or an infinity among the row's nf powers:
+ *          count = -1, pmax = the quiet NaN 0x7fc00000, no segment.
+ *     One workgroup per row, the frames in chunks of ag_activity_chunk() = 1024 whose flags are one ballot word per wave; the
+ *     run state is carried in registers from chunk to chunk, so a row of any length needs 128 bytes of LDS.
+ *                                                                                                 "activity_segments_kernel"
+ *     Refused from host code before any HIP call (AG_ERR_ARG): a negative min_gap, min_run, pad, K or F; B outside 0 .. 65535;
+ *     a win / hop pair ag_frame_power_ok refuses; with B > 0: power_pitch < F, a null nf, len, count or pmax, a null power
+ *     with F > 0, a null seg with K > 0.  B = 0: AG_OK with no launch.
+ * ------------------------------------------------------------------------- */
+int ag_frame_power_ok(int win, int hop);
+int ag_frame_power_tile(int win, int hop);
+int ag_frame_power(const float* src, long long src_pitch, const long long* src_len, long long n_in, long long in_start, int win,
+                   int hop, float* dst, long long dst_pitch, long long f_start, long long n_frames, int B, void* stream);
+int ag_activity_chunk(void);
+int ag_activity_segments(const float* power, long long power_pitch, const int32_t* nf, int F, const long long* len, float ratio,
+                         float floor_, int min_gap, int min_run, int pad, int win, int hop, long long* seg, int K,
+                         int32_t* count, float* pmax, int B, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
