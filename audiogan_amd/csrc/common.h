@@ -39,7 +39,8 @@ struct AgKernelName {          // "base<t0,t1,...>": rocprofv3's spelling withou
 
 // Two-stage reductions (deterministic: no float atomics).  A caller binds a workspace with ag_bind_workspace() right
 // before a reducing entry point; that entry point takes it (the binding is consumed) and sums partial results in a
-// fixed order with ag_slab_reduce().  Without a bound workspace the legacy float-atomic path runs.
+// fixed order with ag_slab_reduce().  Without a bound workspace that is large enough it returns AG_ERR_ARG: there is no
+// atomic path.
 struct AgWs {
   float* p;
   int64_t numel;

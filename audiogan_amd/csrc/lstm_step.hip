@@ -7,7 +7,8 @@
 //  * skinny_gemm_kernel    C[M<=64, N] (+)= A[M,K] * op(B): every wave owns a 32x32 output
 //    tile and a K slice; MFMA operands are fetched STRAIGHT from global/L2 as 16-byte
 //    row pieces (no LDS staging: nothing is reused inside a workgroup), K slices are summed
-//    through LDS inside a workgroup and with fp32 atomics across workgroups.  Up to two
+//    through LDS inside a workgroup and, across workgroups, as slabs of the bound workspace that a
+//    second stage adds in a fixed order (no atomics; no workspace: AG_ERR_ARG).  Up to two
 //    independent problems (the two directions of a bidirectional layer) share one launch.
 //  * lstm_step_fwd_kernel  one LSTM time step fused: gates = pre + [x,h] * [Wx|Whh]^T for the
 //    4 gates of 8 hidden units per workgroup, then the cell non-linearity in the epilogue.
@@ -38,7 +39,7 @@ struct SkinnyP {
   int rb;        // AG_PREC_BF16: operands rounded to bf16 in registers
   int mtiles;    // grid.z = nprob * mtiles
   float* part;   // K split over workgroups (gridDim.y > 1): partial [gridDim.y][nprob][M][N] (two-stage reduction)
-                 // or NULL -> fp32 atomics into C
+                 // in the bound workspace; NULL: K is not split (gridDim.y == 1), the epilogue writes C itself
 };
 
 // A rows m0..m0+31 (k contiguous) x B rows (k contiguous), K range [k0,k1) (multiples of 8).
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd2_kernel(const CellBwd2P p) 
 //   (dgates_k, dc_prev, dh_pass_out) = cell_bwd(dh + dy_k, dc_next, saved gates / cells of step k)
 // One workgroup = 16 clips x 16 hidden units; its 16 waves split K = 4H and are summed through LDS,
 // so the result is complete inside the workgroup (no atomics) and the cell backward runs in the
-// epilogue: ONE launch per time step instead of a pointwise launch plus an atomic product launch.
+// epilogue: ONE launch per time step instead of a pointwise launch plus a two-stage product launch.
 // ------------------------------------------------------------------------------------------
 struct BwdStepDir {
   const float* dg_next;  // product operand A [B,Kp] (row pitch lda): dgates of the previously processed step
@@ -819,8 +820,9 @@ extern "C" int ag_lstm_front_bwd_step(const float* dxa, int lddxa, const float* 
 }
 
 // Whole layer backward through time: per step ONE pointwise launch and ONE K-split skinny
-// product  dh_{k-1} += dgates_k * W_hh  (atomics into the buffer that already holds the
-// pass-through term of padded rows); both directions share each launch.
+// product  dh_{k-1} += dgates_k * W_hh  (its K slices go through the bound workspace and are added,
+// in a fixed order, to the buffer that already holds the pass-through term of padded rows; without a
+// workspace that is large enough: AG_ERR_ARG); both directions share each launch.
 //   gates [ndir][T,B,4H] activated gates (from forward);  dgates [ndir][T,B,4H] (out)
 //   dy [T,B,ndir*H];  dhbuf/dcbuf [ndir][2][B,H] scratch
 extern "C" int ag_lstm_seq_bwd(const float* const* gates, const float* const* whh,

@@ -5,6 +5,8 @@ the kernels assume (device, dtype, unit stride on the last axis, shapes) and enq
 the kernel on torch's current HIP stream.  Nothing here computes on the host and there
 is no fallback: a non-CUDA tensor raises."""
 import ctypes as C
+import os
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -23,45 +25,30 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+BF16 = torch.bfloat16
+_F32_OR_BF16 = (torch.float32, torch.bfloat16)      # a ``dtype`` of _chk / _mat / a check-table row: either storage type
+
+
 def _chk(t, name, dtype=torch.float32):
+    """a device tensor of ``dtype`` (one dtype, or a tuple of the allowed ones); None - an optional tensor - passes"""
     if t is None:
         return
     if not t.is_cuda:
         raise RuntimeError('audiogan_amd: %s must be a CUDA (HIP) tensor; there is no CPU path' % name)
-    if t.dtype != dtype:
-        raise TypeError('audiogan_amd: %s must be %s, got %s' % (name, dtype, t.dtype))
-
-
-BF16 = torch.bfloat16
+    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        want = ' or '.join(str(d_) for d_ in dtype) if isinstance(dtype, tuple) else dtype
+        raise TypeError('audiogan_amd: %s must be %s, got %s' % (name, want, t.dtype))
 
 
 def _is16(t):
     return t is not None and t.dtype == torch.bfloat16
 
 
-def _chk_any(t, name):
-    """fp32 or bfloat16 device tensor"""
-    if t is None:
-        return
-    if not t.is_cuda:
-        raise RuntimeError('audiogan_amd: %s must be a CUDA (HIP) tensor; there is no CPU path' % name)
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError('audiogan_amd: %s must be float32 or bfloat16, got %s' % (name, t.dtype))
-
-
-def _mat_any(t, name):
-    _chk_any(t, name)
-    if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1):
-        raise ValueError('audiogan_amd: %s must be 2-D with unit stride along dim 1' % name)
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
-
-
 # bf16 STORAGE (BASELINE configs[2], round 4): in 'bf16' precision mode the critic's sequence path keeps its activations,
 # their gradients and the GEMM operands as bfloat16 in HBM (ag_gemm_h reads them straight into LDS); fp32 accumulators,
 # master weights, gate pre-activations / cell states of the recurrent kernels and optimiser state are unchanged.
 # AG_BF16_STORE=0 keeps the round-3 form (fp32 in memory, rounded per use) for A/B runs.
-import os as _os1
-BF16_STORE = [_os1.environ.get('AG_BF16_STORE', '1') != '0']
+BF16_STORE = [os.environ.get('AG_BF16_STORE', '1') != '0']
 
 
 def bf16_storage():
@@ -76,9 +63,9 @@ def _bcl(t, name):
     return t.stride(0), t.stride(1)
 
 
-def _mat(t, name):
+def _mat(t, name, dtype=torch.float32):
     """leading dimension of a 2-D row-major view"""
-    _chk(t, name)
+    _chk(t, name, dtype)
     if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1):
         raise ValueError('audiogan_amd: %s must be 2-D with unit stride along dim 1' % name)
     return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
@@ -231,8 +218,6 @@ def wpb_numel(d0, d1, K, stride):
 # ------------------------------------------------------------------------------------
 # descriptor tables (device copies of small C struct arrays), cached by content
 # ------------------------------------------------------------------------------------
-from collections import OrderedDict
-
 _table_cache = OrderedDict()     # descriptor tables created eagerly: LRU, bounded
 _table_pinned = {}               # tables created while a hipGraph was being captured: the graph's copy node re-reads
                                  # the pinned slot and its kernels read the device table on every replay - never evicted
@@ -317,8 +302,100 @@ def reserve_table_arena():
 
 
 # ------------------------------------------------------------------------------------
+# per-kernel timing hook for bench.py's roofline figure: HIP events recorded on the launch
+# stream around the launches of ONE kernel class (or all of them in the discovery pass).
+# A wrapper is timed iff its ``def`` carries ``@_timed(...)``; its work model stands right above it.
+# ------------------------------------------------------------------------------------
+class Profiler(object):
+    enabled = False
+    only = None          # kernel name (as ag_last_kernel / rocprofv3 spell it) or class key to time, or None = all
+    records = []         # (key, flops, bytes, ev_start, ev_stop)
+
+    @classmethod
+    def start(cls, only=None):
+        cls.enabled, cls.only, cls.records = True, only, []
+
+    @classmethod
+    def stop(cls):
+        cls.enabled = False
+        torch.cuda.synchronize()
+        out = {}
+        for key, fl, by, e0, e1, nl in cls.records:
+            r = out.setdefault(key, dict(n=0, ms=0.0, flops=0.0, bytes=0.0))
+            r['n'] += nl
+            r['ms'] += e0.elapsed_time(e1)
+            r['flops'] += fl
+            r['bytes'] += by
+        cls.records = []
+        return out
+
+
+def _bf16_tag():
+    """bf16 mode: the persistent recurrent kernels run their v_mfma_f32_*_bf16 instantiation"""
+    return '<bf16>' if lib.ag_get_precision() == 1 else ''
+
+
+def _call_sig(a, k):
+    """everything about a call that a dispatch rule could look at, without knowing any rule: per argument a tensor's shape,
+    strides, dtype and alignment, a list element by element, anything else by value; plus the precision mode.  The result
+    is a dict key: every other argument must be hashable (numbers, bools, None, strings - all the four naming wrappers take)"""
+    def one(v):
+        if isinstance(v, torch.Tensor):
+            return tuple(v.shape), v.stride(), v.dtype, v.data_ptr() % 16
+        if isinstance(v, (list, tuple)):
+            return tuple(one(e) for e in v)
+        return v
+    return tuple(one(v) for v in a), tuple((n, one(k[n])) for n in sorted(k)), lib.ag_get_precision()
+
+
+def _timed(work=None, name=None):
+    """``@_timed(work)`` on a wrapper's ``def``: under the Profiler its calls are timed and filed.  ``work``: a model
+    _work_*(same arguments as the wrapped call) -> (key, flops, bytes[, launches]), the algorithmic work of the call from its
+    shapes; key None: the library chose among kernel forms and names the one it launched itself (ag_last_kernel).  No
+    model: filed under ``name`` (default: the function's own) with no work.  The wrapper shows both as ``timed_work`` and
+    ``timed_name`` (tests/test_launch_layer.py pins the whole set)."""
+    def deco(fn):
+        me = name or fn.__name__
+        seen = {}       # call signature -> the kernel name the library reported for it last time (only steers `only`)
+
+        def wrapped(*a, **k):
+            if not Profiler.enabled:
+                return fn(*a, **k)
+            w_ = work(*a, **k) if work is not None else (me, 0.0, 0.0)
+            key, fl, by = w_[:3]
+            nl = w_[3] if len(w_) > 3 else 1        # launches behind this call (a whole recurrent layer pass: T)
+            only = Profiler.only
+            if key is None:
+                sig = _call_sig(a, k)
+                if only is not None and seen.get(sig, only) != only:     # (a signature not seen yet is timed and learnt)
+                    return fn(*a, **k)
+            elif only is not None and key != only:
+                return fn(*a, **k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*a, **k)
+            e1.record()
+            if key is None:
+                key = seen[sig] = lib.ag_last_kernel().decode()
+            Profiler.records.append((key, fl, by, e0, e1, nl))
+            return r
+        wrapped.__name__ = me
+        wrapped.__doc__ = fn.__doc__
+        wrapped.__module__ = __name__
+        wrapped.timed_work, wrapped.timed_name = work, me
+        return wrapped
+    return deco
+
+
+def _work_named(*a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    return None, 0.0, 0.0
+
+
+# ------------------------------------------------------------------------------------
 # weight norm
 # ------------------------------------------------------------------------------------
+@_timed()
 def weight_norm_fwd(entries):
     """entries: list of dict(v, g, w=None, wpa=None, wpb=None, stride=1, pad=0).  v is the
     parameter tensor ([d0], [d0,d1] or [d0,d1,K]); outputs are written in place.  ``pad``: the conv padding the
@@ -351,6 +428,7 @@ def weight_norm_fwd(entries):
     check(lib.ag_weight_norm_fwd(_p(tab), len(descs), max_rows, _stream()), 'ag_weight_norm_fwd')
 
 
+@_timed()
 def weight_norm_bwd(entries):
     """entries: list of dict(v, g, dw, dv, dg[, accumulate]); dv/dg are written (or added to)."""
     descs, max_rows = [], 1
@@ -384,6 +462,14 @@ def prep_conv_weight(w, wpa, wpb, stride, pad=0):
 # ------------------------------------------------------------------------------------
 # conv engine
 # ------------------------------------------------------------------------------------
+def _work_conv(x, wp, y, K_, stride, pad, mode, *a_, **kw):
+    B, Cc, Lin = x.shape
+    _, O, Lout = y.shape
+    macs = B * O * Lout * Cc * K_ if mode == 0 else B * Cc * Lin * O * K_
+    return None, 2.0 * macs, 4.0 * (x.numel() + y.numel() + O * Cc * K_)
+
+
+@_timed(_work_conv)
 def conv_engine(x, wp, y, K, stride, pad, mode, bias=None, res=None, lens=None, act=ACT_NONE,
                 slope=LEAKY_SLOPE, accumulate=False, wp_pad=0):
     """mode 0: y[b,o,t] = sum W x[b,c,s*t+k-p]   (wp = gather layout of the weight)
@@ -415,6 +501,13 @@ def conv_engine(x, wp, y, K, stride, pad, mode, bias=None, res=None, lens=None, 
     check(lib.ag_conv1d_engine(C.byref(a), _stream()), 'ag_conv1d_engine')
 
 
+def _work_wgrad(sh, lg, dw, K_, stride, pad):
+    B, A, Lsh = sh.shape
+    Cc = lg.size(1)
+    return None, 2.0 * B * A * Lsh * Cc * K_, 4.0 * (sh.numel() + lg.numel() + dw.numel())
+
+
+@_timed(_work_wgrad)
 def conv_wgrad(sh, lg, dw, K, stride, pad):
     """dw[a,c,k] += sum_{b,t} sh[b,a,t] * lg[b,c,s*t+k-p];  dw: [A,C,K] contiguous."""
     sh_bs, sh_cs = _bcl(sh, 'sh')
@@ -428,6 +521,7 @@ def conv_wgrad(sh, lg, dw, K, stride, pad):
                               K, stride, pad, _stream()), 'ag_conv1d_wgrad')
 
 
+@_timed()
 def channel_sum(dy, db, accumulate=True):
     """db[c] (+)= sum_{b,t} dy[b,c,t]"""
     bs, cs = _bcl(dy, 'dy')
@@ -438,6 +532,7 @@ def channel_sum(dy, db, accumulate=True):
     check(lib.ag_channel_sum(_p(dy), bs, cs, _p(db), B, Cc, L, int(bool(accumulate)), _stream()), 'ag_channel_sum')
 
 
+@_timed()
 def leaky_bwd(dy, y, dpre, lens=None, slope=LEAKY_SLOPE, add_into=None, bias_grad=None):
     """dpre = dy * (y > 0 ? 1 : slope) * (t < lens[b]); all [B,C,L] views; dpre may alias dy.
     add_into (optional [B,C,L] view, must not overlap dpre): add_into += dpre.
@@ -459,6 +554,13 @@ def leaky_bwd(dy, y, dpre, lens=None, slope=LEAKY_SLOPE, add_into=None, bias_gra
 # ------------------------------------------------------------------------------------
 # GEMM
 # ------------------------------------------------------------------------------------
+def _work_gemm(A, B, Cm, ta=False, tb=False, *a_, **kw):
+    M, N = Cm.shape
+    Kd = A.size(0) if ta else A.size(1)
+    return None, 2.0 * M * N * Kd, 4.0 * (M * Kd + N * Kd + M * N)
+
+
+@_timed(_work_gemm)
 def gemm(A, B, Cm, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, res=None, act=ACT_NONE,
          slope=LEAKY_SLOPE, defer=False):
     """Cm[M,N] = act(alpha * op(A) @ op(B) + beta*Cm + bias + res).
@@ -491,10 +593,11 @@ def gemm(A, B, Cm, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, res=None,
             lib.ag_defer_reduces(3)
 
 
+@_timed()
 def col_sum(X, out, accumulate=True, defer=True):
     """out[n] (+)= sum_m X[m,n].  ``defer=False``: complete when the call returns (in stream order) also inside a recording
     ``deferred_reduces`` scope - for sums that are read before that scope closes."""
-    ldx = _mat_any(X, 'X')
+    ldx = _mat(X, 'X', _F32_OR_BF16)
     _chk(out, 'out')
     M, N = X.shape
     assert out.numel() == N and out.is_contiguous()
@@ -512,6 +615,7 @@ def col_sum(X, out, accumulate=True, defer=True):
 # ------------------------------------------------------------------------------------
 # LSTM cell pointwise
 # ------------------------------------------------------------------------------------
+@_timed()
 def lstm_cell_fwd(gates, c_prev, c_out, h_out=None, y_out=None, h_prev=None, valid=None, t=0):
     ldg = _mat(gates, 'gates')
     B, H4 = gates.shape
@@ -526,6 +630,7 @@ def lstm_cell_fwd(gates, c_prev, c_out, h_out=None, y_out=None, h_prev=None, val
                                _stream()), 'ag_lstm_cell_fwd')
 
 
+@_timed()
 def lstm_cell_bwd(gates_act, c_prev, c_new, dh, dy, dc_next, dgates, dc_prev, dh_pass=None,
                   valid=None, t=0):
     """dh: gradient from later steps (or None), dy: gradient of this step's output (or None)"""
@@ -546,6 +651,7 @@ def lstm_cell_bwd(gates_act, c_prev, c_new, dh, dy, dc_next, dgates, dc_prev, dh
 # ------------------------------------------------------------------------------------
 # BCE / activations
 # ------------------------------------------------------------------------------------
+@_timed()
 def bce_logits_fwd(x, target, nframes, per_sample, loss, scale):
     """per_sample[b] = masked sum; loss[0] += scale * sum_b per_sample[b]/n[b]"""
     ldx = _mat(x, 'x')
@@ -555,6 +661,7 @@ def bce_logits_fwd(x, target, nframes, per_sample, loss, scale):
                                 float(scale), B, T, _stream()), 'ag_bce_logits_fwd')
 
 
+@_timed()
 def bce_logits_bwd(x, target, nframes, gscale, scale, dx):
     ldx, lddx = _mat(x, 'x'), _mat(dx, 'dx')
     _chk(nframes, 'nframes', torch.int64); _chk(gscale, 'gscale')
@@ -585,12 +692,14 @@ def bce_logits_bwd_strided(x, target, nframes, gscale, scale, dx, target_rows=No
           'ag_bce_logits_bwd_strided')
 
 
+@_timed()
 def act_fwd(x, y, act, slope=LEAKY_SLOPE):
     _chk(x, 'x'); _chk(y, 'y')
     assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
     check(lib.ag_act_fwd(_p(x), _p(y), x.numel(), act, slope, _stream()), 'ag_act_fwd')
 
 
+@_timed()
 def act_bwd(dy, y, dx, act, slope=LEAKY_SLOPE):
     for t_, n in ((dy, 'dy'), (y, 'y'), (dx, 'dx')):
         _chk(t_, n)
@@ -602,12 +711,12 @@ def act_bwd(dy, y, dx, act, slope=LEAKY_SLOPE):
 def bct_to_tbc(x, out=None, out_dtype=None):
     """[B,C,T] (any batch / channel pitch, time contiguous) -> contiguous [T,B,C] (ag_transpose_batched); fp32 or bf16 on
     either side (``out_dtype``: default = x's)"""
-    _chk_any(x, 'x')
+    _chk(x, 'x', _F32_OR_BF16)
     B, Cc, T = x.shape
     assert x.stride(2) == 1
     if out is None:
         out = torch.empty(T, B, Cc, device=x.device, dtype=out_dtype or x.dtype)
-    _chk_any(out, 'out')
+    _chk(out, 'out', _F32_OR_BF16)
     check(lib.ag_transpose_batched(_p(x), int(_is16(x)), x.stride(0), x.stride(1), _p(out), int(_is16(out)), Cc, B * Cc, B, Cc,
                                    T, _stream()), 'ag_transpose_batched')
     return out
@@ -615,12 +724,12 @@ def bct_to_tbc(x, out=None, out_dtype=None):
 
 def tbc_to_bct(x, out=None, out_dtype=None):
     """contiguous [T,B,C] -> contiguous [B,C,T] (ag_transpose_batched); fp32 or bf16 on either side"""
-    _chk_any(x, 'x')
+    _chk(x, 'x', _F32_OR_BF16)
     T, B, Cc = x.shape
     assert x.is_contiguous()
     if out is None:
         out = torch.empty(B, Cc, T, device=x.device, dtype=out_dtype or x.dtype)
-    _chk_any(out, 'out')
+    _chk(out, 'out', _F32_OR_BF16)
     check(lib.ag_transpose_batched(_p(x), int(_is16(x)), Cc, B * Cc, _p(out), int(_is16(out)), Cc * T, T, B, T, Cc, _stream()),
           'ag_transpose_batched')
     return out
@@ -631,9 +740,10 @@ def rowdot_ok(x, w):
     return x.dim() == 2 and x.stride(1) == 1 and w.numel() == x.size(1) and w.is_contiguous()
 
 
+@_timed()
 def rowdot_fwd(x, w, bias, y):
     """y[m] = x[m,:] . w + bias[0]; y: [M] or [M,1] of any stride; x fp32 or bf16"""
-    ldx = _mat_any(x, 'x')
+    ldx = _mat(x, 'x', _F32_OR_BF16)
     _chk(w, 'w'); _chk(bias, 'bias'); _chk(y, 'y')
     M, Kd = x.shape
     assert rowdot_ok(x, w) and y.numel() == M
@@ -641,15 +751,16 @@ def rowdot_fwd(x, w, bias, y):
     check(lib.ag_rowdot_fwd(_p(x), int(_is16(x)), ldx, _p(w), _p(bias), _p(y), ldy, M, Kd, _stream()), 'ag_rowdot_fwd')
 
 
+@_timed()
 def rowdot_bwd(dy, x, w, dx=None, dw=None, db=None, gate=False, slope=LEAKY_SLOPE, accumulate=True):
     """backward of a one-output Linear in ONE pass over x: dx = dy (x) w (times LeakyReLU'(x) when ``gate``: x is the saved
     output of the LeakyReLU below), dw (+)= dy^T x, db (+)= sum dy.  dw [1,K] / [K] and db [1] must be adjacent in memory
     (db right behind dw: one gradient row), as the views of WNGroup.zero_dws are; dy: [M] or [M,1] of any stride."""
-    ldx = _mat_any(x, 'x')
-    _chk(dy, 'dy'); _chk(w, 'w'); _chk_any(dx, 'dx'); _chk(dw, 'dw'); _chk(db, 'db')
+    ldx = _mat(x, 'x', _F32_OR_BF16)
+    _chk(dy, 'dy'); _chk(w, 'w'); _chk(dx, 'dx', _F32_OR_BF16); _chk(dw, 'dw'); _chk(db, 'db')
     M, Kd = x.shape
     assert rowdot_ok(x, w) and dy.numel() == M
-    lddx = _mat_any(dx, 'dx') if dx is not None else 0
+    lddx = _mat(dx, 'dx', _F32_OR_BF16) if dx is not None else 0
     assert dx is None or (tuple(dx.shape) == (M, Kd) and dx.dtype == x.dtype), 'x and dx share a storage type'
     h16 = int(_is16(x))
     if dw is not None:
@@ -660,6 +771,7 @@ def rowdot_bwd(dy, x, w, dx=None, dw=None, db=None, gate=False, slope=LEAKY_SLOP
                             int(bool(accumulate)), M, Kd, int(bool(gate)), slope, _stream()), 'ag_rowdot_bwd')
 
 
+@_timed()
 def to_bf16(src, out=None):
     """a bfloat16 image of a contiguous or row-pitched 2-D fp32 tensor / of any contiguous fp32 tensor (ag_to_bf16_2d)"""
     _chk(src, 'src')
@@ -690,12 +802,20 @@ def gemm_h_ok(A, B, ta, tb):
     return bool(lib.ag_gemm_h_ok(M, N, Kd, int(ta), int(tb), lda, ldb)) and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
 
 
+def _work_gemm_h(A, B, C=None, C16=None, ta=False, tb=False, *a_, **kw):
+    out = C if C is not None else C16
+    M, N = out.shape
+    Kd = A.size(0) if ta else A.size(1)
+    return None, 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd) + (4.0 if C is not None else 2.0) * M * N
+
+
+@_timed(_work_gemm_h)
 def gemm_h(A, B, C=None, C16=None, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, res=None, gate=None, act=ACT_NONE,
            slope=LEAKY_SLOPE, defer=False):
     """C / C16 [M,N] = act(alpha * op(A) @ op(B) + beta * C + bias + res) on operands STORED as bfloat16 (ag_gemm_h).
     C: fp32 output, C16: bf16 output (either or both); res: fp32 or bf16 residual (with ACT_LEAKY_GATE: the saved activation);
     gate: bf16 saved LeakyReLU output applied after bias / res.  ``defer`` as for gemm()."""
-    lda, ldb = _mat_any(A, 'A'), _mat_any(B, 'B')
+    lda, ldb = _mat(A, 'A', _F32_OR_BF16), _mat(B, 'B', _F32_OR_BF16)
     assert _is16(A) and _is16(B), 'gemm_h: bf16 operands'
     out = C if C is not None else C16
     M, N = out.shape
@@ -708,16 +828,16 @@ def gemm_h(A, B, C=None, C16=None, ta=False, tb=False, alpha=1.0, beta=0.0, bias
         assert tuple(C.shape) == (M, N)
     if C16 is not None:
         _chk(C16, 'C16', torch.bfloat16)
-        ldc16 = _mat_any(C16, 'C16')
+        ldc16 = _mat(C16, 'C16', _F32_OR_BF16)
         assert tuple(C16.shape) == (M, N)
     r32 = res if (res is not None and not _is16(res)) else None
     r16 = res if _is16(res) else None
     if res is not None:
         assert tuple(res.shape) == (M, N)
-        ldres, ldres16 = (_mat(r32, 'res') if r32 is not None else 0), (_mat_any(r16, 'res') if r16 is not None else 0)
+        ldres, ldres16 = (_mat(r32, 'res') if r32 is not None else 0), (_mat(r16, 'res', _F32_OR_BF16) if r16 is not None else 0)
     if gate is not None:
         _chk(gate, 'gate', torch.bfloat16)
-        ldg = _mat_any(gate, 'gate')
+        ldg = _mat(gate, 'gate', _F32_OR_BF16)
         assert tuple(gate.shape) == (M, N)
     if bias is not None:
         _chk(bias, 'bias')
@@ -735,13 +855,7 @@ def gemm_h(A, B, C=None, C16=None, ta=False, tb=False, alpha=1.0, beta=0.0, bias
             lib.ag_defer_reduces(3)
 
 
-def _work_gemm_h(A, B, C=None, C16=None, ta=False, tb=False, *a_, **kw):
-    out = C if C is not None else C16
-    M, N = out.shape
-    Kd = A.size(0) if ta else A.size(1)
-    return None, 2.0 * M * N * Kd, 2.0 * (M * Kd + N * Kd) + (4.0 if C is not None else 2.0) * M * N
-
-
+@_timed()
 def build_zc(z, c, out=None):
     """zc[t,b,:] = [z[b,t,:] | c[b,:]]: z [B,T,ns], c [B,es] -> contiguous [T,B,ns+es] (ag_build_zc; audiogan.py:433-439)"""
     _chk(z, 'z'); _chk(c, 'c')
@@ -754,6 +868,7 @@ def build_zc(z, c, out=None):
     return out
 
 
+@_timed()
 def critic_batch(xa, na=None, xb=None, nb=None, len_a=None, len_b=None, prods=(), ca=None, cb=None):
     """the critic's minibatch in ONE launch (ag_critic_batch): rows [xa + na ; xb + nb] -> x [nA+nB, L]; the rows' lengths
     after every conv layer, lens [len(prods), nA+nB] int64 with lens[i] = ceil(len / prods[i]) (len_a / len_b None: L); the
@@ -785,6 +900,7 @@ def critic_batch(xa, na=None, xb=None, nb=None, len_a=None, len_b=None, prods=()
     return x, lens, c
 
 
+@_timed()
 def axpby(x, y, a, b):
     """y = a*x + b*y (contiguous)"""
     _chk(x, 'x'); _chk(y, 'y')
@@ -805,6 +921,7 @@ def _opt_table(params, grads, s1, s2):
     return _table('opt', descs, params[0].device)
 
 
+@_timed()
 def grad_norms(params, grads, s1, s2, norms, norm_sum, flags, grad_scale=1.0, step_dev=None, finish=True):
     """norms[i] = ||grads[i]*grad_scale||; norm_sum[0] = sum_i norms[i]; flags = NaN/BIG bits (written).  ``finish=False``:
     only the per-chunk partial sums are computed; returns the workspace holding them, to be handed to ``opt_step(part=...)``
@@ -820,6 +937,7 @@ def grad_norms(params, grads, s1, s2, norms, norm_sum, flags, grad_scale=1.0, st
     return ws
 
 
+@_timed()
 def opt_step(params, grads, s1, s2, norms, kind, lr, clip, grad_scale, a1, b2, eps, step, step_dev=None, part=None,
              norm_sum=None, flags=None):
     """``part``: the workspace ``grad_norms(finish=False)`` returned - this launch then also finishes the norms"""
@@ -843,7 +961,6 @@ def ema_plan(shadows, params):
     chunk inside it), built once per list of tensors.  The bytes go through ``_table`` on every ``ema_update``, so the
     device copy is cached / pinned under capture exactly as the optimiser's table is.  A caller that keeps its tensors
     (optim.EMA) may keep the plan and hand it back: the per-tensor checks then run once, not per launch."""
-    import numpy as np
     assert len(shadows) == len(params) and len(params) > 0
     for e, p in zip(shadows, params):
         _chk(e, 'shadow'); _chk(p, 'param')
@@ -868,6 +985,11 @@ def ema_plan(shadows, params):
     return plan
 
 
+def _work_ema(shadows, params, *a_, **kw):
+    return 'ema_update_kernel', 0.0, 12.0 * sum(p.numel() for p in params)
+
+
+@_timed(_work_ema)
 def ema_update(shadows, params, decay, warmup, step_dev, step0, k=0, plan=None):
     """shadows[i] = lerp(shadows[i], params[i], 1 - d) for the whole list in ONE launch (ag_ema_update): per element
     ``e = fmaf(1 - d, p - e, e)`` in fp32; d = decay, or with ``warmup`` min(decay, (1 + k) / (10 + k)) where
@@ -885,116 +1007,6 @@ def ema_update(shadows, params, decay, warmup, step_dev, step0, k=0, plan=None):
                             int(bool(warmup)), _p(step_dev), int(step0), int(k), _stream()), 'ag_ema_update')
 
 
-def _work_ema(shadows, params, *a_, **kw):
-    return 'ema_update_kernel', 0.0, 12.0 * sum(p.numel() for p in params)
-
-
-# ------------------------------------------------------------------------------------
-# per-kernel timing hook for bench.py's roofline figure: HIP events recorded on the launch
-# stream around the launches of ONE kernel class (or all of them in the discovery pass).
-# ------------------------------------------------------------------------------------
-class Profiler(object):
-    enabled = False
-    only = None          # kernel name (as ag_last_kernel / rocprofv3 spell it) or class key to time, or None = all
-    records = []         # (key, flops, bytes, ev_start, ev_stop)
-
-    @classmethod
-    def start(cls, only=None):
-        cls.enabled, cls.only, cls.records = True, only, []
-
-    @classmethod
-    def stop(cls):
-        cls.enabled = False
-        torch.cuda.synchronize()
-        out = {}
-        for key, fl, by, e0, e1, nl in cls.records:
-            r = out.setdefault(key, dict(n=0, ms=0.0, flops=0.0, bytes=0.0))
-            r['n'] += nl
-            r['ms'] += e0.elapsed_time(e1)
-            r['flops'] += fl
-            r['bytes'] += by
-        cls.records = []
-        return out
-
-
-def _bf16_tag():
-    """bf16 mode: the persistent recurrent kernels run their v_mfma_f32_*_bf16 instantiation"""
-    return '<bf16>' if lib.ag_get_precision() == 1 else ''
-
-
-# _work_*(same arguments as the wrapped call) -> (key, flops, bytes[, launches]): the algorithmic work of the call from its
-# shapes.  key None: the library chose among kernel forms and names the one it launched itself (ag_last_kernel).
-def _work_gemm(A, B, Cm, ta=False, tb=False, *a_, **kw):
-    M, N = Cm.shape
-    Kd = A.size(0) if ta else A.size(1)
-    return None, 2.0 * M * N * Kd, 4.0 * (M * Kd + N * Kd + M * N)
-
-
-def _work_conv(x, wp, y, K_, stride, pad, mode, *a_, **kw):
-    B, Cc, Lin = x.shape
-    _, O, Lout = y.shape
-    macs = B * O * Lout * Cc * K_ if mode == 0 else B * Cc * Lin * O * K_
-    return None, 2.0 * macs, 4.0 * (x.numel() + y.numel() + O * Cc * K_)
-
-
-def _work_wgrad(sh, lg, dw, K_, stride, pad):
-    B, A, Lsh = sh.shape
-    Cc = lg.size(1)
-    return None, 2.0 * B * A * Lsh * Cc * K_, 4.0 * (sh.numel() + lg.numel() + dw.numel())
-
-
-def _call_sig(a, k):
-    """everything about a call that a dispatch rule could look at, without knowing any rule: per argument a tensor's shape,
-    strides, dtype and alignment, a list element by element, anything else by value; plus the precision mode.  The result
-    is a dict key: every other argument must be hashable (numbers, bools, None, strings - all the four naming wrappers take)"""
-    def one(v):
-        if isinstance(v, torch.Tensor):
-            return tuple(v.shape), v.stride(), v.dtype, v.data_ptr() % 16
-        if isinstance(v, (list, tuple)):
-            return tuple(one(e) for e in v)
-        return v
-    return tuple(one(v) for v in a), tuple((n, one(k[n])) for n in sorted(k)), lib.ag_get_precision()
-
-
-def _instrument(name, work):
-    fn = globals()[name]
-    seen = {}       # call signature -> the kernel name the library reported for it last time (only steers `only`)
-
-    def wrapped(*a, **k):
-        if not Profiler.enabled:
-            return fn(*a, **k)
-        w_ = work(*a, **k) if work is not None else (name, 0.0, 0.0)
-        key, fl, by = w_[:3]
-        nl = w_[3] if len(w_) > 3 else 1        # launches behind this call (a whole recurrent layer pass: T)
-        only = Profiler.only
-        if key is None:
-            sig = _call_sig(a, k)
-            if only is not None and seen.get(sig, only) != only:     # (a signature not seen yet is timed and learnt)
-                return fn(*a, **k)
-        elif only is not None and key != only:
-            return fn(*a, **k)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **k)
-        e1.record()
-        if key is None:
-            key = seen[sig] = lib.ag_last_kernel().decode()
-        Profiler.records.append((key, fl, by, e0, e1, nl))
-        return r
-    wrapped.__name__ = name
-    wrapped.__doc__ = fn.__doc__
-    wrapped.__module__ = __name__
-    globals()[name] = wrapped
-
-
-for _n, _w in (('gemm', _work_gemm), ('conv_engine', _work_conv), ('conv_wgrad', _work_wgrad),
-               ('channel_sum', None), ('leaky_bwd', None), ('col_sum', None), ('lstm_cell_fwd', None),
-               ('lstm_cell_bwd', None), ('weight_norm_fwd', None), ('weight_norm_bwd', None),
-               ('bce_logits_fwd', None), ('bce_logits_bwd', None), ('act_fwd', None), ('act_bwd', None),
-               ('axpby', None), ('grad_norms', None), ('opt_step', None), ('ema_update', _work_ema)):
-    _instrument(_n, _w)
-
-
 # ------------------------------------------------------------------------------------
 # skinny products / fused recurrent steps (lstm_step.hip)
 # ------------------------------------------------------------------------------------
@@ -1003,7 +1015,7 @@ def _al16(t):
 
 
 def skinny_ok(A, B, tb):
-    """can ag_skinny_gemm take this product? (M <= 64, K % 8 == 0, 16-byte aligned rows)"""
+    """can ag_skinny_gemm take this product? (M <= 256, K % 8 == 0, 16-byte aligned rows)"""
     M, Kd = A.shape
     ok = M <= 256 and Kd % 8 == 0 and A.stride(1) == 1 and A.stride(0) % 4 == 0 and _al16(A)
     if tb:
@@ -1011,8 +1023,16 @@ def skinny_ok(A, B, tb):
     return ok
 
 
+def _work_skinny(A, B, Cm, tb=False, *a_, **kw):
+    M, N = Cm.shape
+    return 'skinny_gemm_kernel', 2.0 * M * N * A.size(1), \
+        4.0 * (A.numel() + N * A.size(1) + M * N)
+
+
+@_timed(_work_skinny)
 def skinny_gemm(A, B, Cm, tb=False, beta=0.0, bias=None, act=ACT_NONE, slope=LEAKY_SLOPE, atomic=False):
-    """Cm[M<=64,N] = act(A @ op(B) + beta*Cm + bias), or with atomic=True: Cm += A @ op(B) (+bias)"""
+    """Cm[M<=256,N] = act(A @ op(B) + beta*Cm + bias), or with atomic=True: Cm += A @ op(B) (+bias).  ``atomic`` means
+    "accumulate through the two-stage workspace" (bound here, summed in a fixed order); no atomic instruction is involved"""
     lda, ldb, ldc = _mat(A, 'A'), _mat(B, 'B'), _mat(Cm, 'C')
     M, N = Cm.shape
     Kd = A.size(1)
@@ -1057,6 +1077,13 @@ def lstm_step_ok(B, H, x=None, wx=None):
     return ok
 
 
+def _work_step(gates_pre, x, wx, h_prev, whh, *a_, **kw):
+    B, H4 = gates_pre.shape
+    Kd = H4 // 4 + (x.size(1) if x is not None else 0)
+    return 'lstm_step_fwd_kernel', 2.0 * B * H4 * Kd, 4.0 * (H4 * Kd + 3 * B * H4)
+
+
+@_timed(_work_step)
 def lstm_step_fwd(gates_pre, x, wx, h_prev, whh, c_prev, c_out, h_out, first_step):
     """fused LSTMCell step; gates_pre [B,4H] contiguous is overwritten with the activated gates"""
     for t_, n in ((gates_pre, 'gates_pre'), (h_prev, 'h_prev'), (whh, 'whh'), (c_prev, 'c_prev'),
@@ -1078,10 +1105,44 @@ def _ptr_table(tensors):
     return arr
 
 
-# ---- persistent (weights-resident) layer pass: workspace per device, status word, switch -------------------------
-import os as _os
+def _rows(t, name, B, n):
+    """row pitch of a [B, n] view with unit stride along dim 1 (a slab channel, a column block)"""
+    _chk(t, name)
+    assert t.dim() == 2 and tuple(t.shape) == (B, n) and (n == 1 or t.stride(1) == 1), (name, tuple(t.shape), t.stride())
+    return t.stride(0) if B > 1 else max(t.stride(0), n)
 
-PERSIST = [_os.environ.get('AG_LSTM_PERSIST', '1') != '0']
+
+_PITCHED = 'pitched'      # mark in a _check_table row: a 2-D view of unit stride along dim 1 and any row pitch
+
+
+def _check_table(table):
+    """the tensor checks of the recurrent launches.  Rows (tensor, name, shape[, kind]): a device tensor of that shape and of
+    the dtype ``kind`` (fp32 by default; _F32_OR_BF16: either), dense unless ``kind`` is _PITCHED (fp32; channel 0 of a slab,
+    a column block of a weight).  A tensor that is None (an optional one) is skipped.  Returns {name: row pitch} of the
+    _PITCHED rows (0: None)"""
+    ld = {}
+    for t, name, shp, *kind in table:
+        if kind == [_PITCHED]:
+            ld[name] = _rows(t, name, *shp) if t is not None else 0
+        elif t is not None:
+            _chk(t, name, *kind)
+            assert t.is_contiguous() and tuple(t.shape) == shp, (name, tuple(t.shape), shp)
+    return ld
+
+
+def _per_dir(ndir, *lists):
+    """_check_table rows of an LSTM layer pass: (list, name, shape[, kind]), a list of one tensor per direction or None (an
+    optional list), gives one row per direction, named name[d]"""
+    rows = []
+    for lst, name, *rest in lists:
+        if lst is not None:
+            assert len(lst) == ndir, (name, len(lst), ndir)
+            rows += [(t, '%s[%d]' % (name, d)) + tuple(rest) for d, t in enumerate(lst)]
+    return rows
+
+
+# ---- persistent (weights-resident) layer pass: workspace per device, status word, switch -------------------------
+PERSIST = [os.environ.get('AG_LSTM_PERSIST', '1') != '0']
 _persist_ws = {}
 _ncu = {}
 
@@ -1093,8 +1154,14 @@ def _n_cu(dev):
     return n
 
 
+def _persist_ok(rule, dims, dev, on=True):
+    """the one rule by which a persistent launch is offered: PERSIST[0] and the launch's own switches (``on``), a CUDA device,
+    and the library's shape rule for the device's CU count, lib.<rule>(*dims, n_cu)"""
+    return bool(PERSIST[0] and on and torch.device(dev).type == 'cuda' and rule(*dims, _n_cu(dev)))
+
+
 def lstm_persist_ok(B, H, ndir, dev):
-    return bool(PERSIST[0] and torch.device(dev).type == 'cuda' and lib.ag_lstm_persist_ok(B, H, ndir, _n_cu(dev)))
+    return _persist_ok(lib.ag_lstm_persist_ok, (B, H, ndir), dev)
 
 
 _PERSIST_WS_MIN = 8 << 20      # covers every BASELINE shape (biLSTM at 256 clips, H 768: 3.2 MB; the generator front: 0.7 MB)
@@ -1159,22 +1226,27 @@ def lstm_seq_fwd_persist(pre, whh, c_all, y, valid, static=None):
     ndir = len(pre)
     T, B, H4 = pre[0].shape
     H = H4 // 4
-    for d in range(ndir):
-        for t_, shp in ((pre[d], (T, B, 4 * H)), (whh[d], (4 * H, H)), (c_all[d], (T + 1, B, H))):
-            _chk(t_, 'lstm_seq tensor')
-            assert t_.is_contiguous() and tuple(t_.shape) == shp, (tuple(t_.shape), shp)
-    _chk_any(y, 'y'); _chk(valid, 'valid', torch.int64)
-    assert y.is_contiguous() and tuple(y.shape) == (T, B, ndir * H)
-    if static is not None:
-        assert len(static) == ndir
-        for t_ in static:
-            _chk(t_, 'static')
-            assert t_.is_contiguous() and tuple(t_.shape) == (B, 4 * H)
+    _check_table(_per_dir(ndir, (pre, 'pre', (T, B, 4 * H)), (whh, 'whh', (4 * H, H)), (c_all, 'c_all', (T + 1, B, H)),
+                          (static, 'static', (B, 4 * H))) + [(y, 'y', (T, B, ndir * H), _F32_OR_BF16)])
+    _chk(valid, 'valid', torch.int64)
     nb = int(lib.ag_lstm_persist_ws_bytes(B, H, ndir))
     ws = _persist_workspace(y.device, nb)
     check(lib.ag_lstm_seq_fwd_persist(_ptr_table(pre), _ptr_table(whh), _ptr_table(c_all), _p(y), int(_is16(y)), _p(valid),
                                       _ptr_table(static) if static is not None else None, _p(ws), ws.numel(),
                                       T, B, H, ndir, _n_cu(y.device), _stream()), 'ag_lstm_seq_fwd_persist')
+
+
+def _work_seq_fwd_persist(pre, whh, c_all, y, valid, static=None):
+    T, B, H4 = pre[0].shape
+    nd = len(pre)
+    # one launch = the whole layer pass: T steps of 2*B*4H*H flops per direction; algorithmic bytes: W_hh ONCE
+    # + gates in/out, cells, outputs per step
+    return 'lstm_persist_fwd_kernel' + _bf16_tag(), T * 2.0 * nd * B * H4 * (H4 // 4), \
+        4.0 * nd * (H4 * (H4 // 4) + T * 3 * B * H4), 1
+
+
+# (the public wrapper stays untimed: lstm_seq_fwd goes through this name)
+_lstm_seq_fwd_persist_call = _timed(_work_seq_fwd_persist, name='_lstm_seq_fwd_persist_call')(lstm_seq_fwd_persist)
 
 
 def lstm_seq_fwd(pre, whh, c_all, hbuf, y, valid, static=None):
@@ -1190,57 +1262,27 @@ def lstm_seq_fwd(pre, whh, c_all, hbuf, y, valid, static=None):
     _lstm_seq_fwd_range(pre, whh, c_all, hbuf, y, valid, 0, T, static)
 
 
-def _lstm_seq_fwd_persist_call(pre, whh, c_all, y, valid, static=None):
-    lstm_seq_fwd_persist(pre, whh, c_all, y, valid, static)
+def _work_seq_fwd(pre, whh, c_all, hbuf, y, valid, k0, k1, *a_, **kw):
+    T, B, H4 = pre[0].shape
+    nd, n = len(pre), k1 - k0
+    return 'lstm_step_fwd_kernel', n * 2.0 * nd * B * H4 * (H4 // 4), n * 4.0 * nd * (H4 * (H4 // 4) + 3 * B * H4), n
 
 
+@_timed(_work_seq_fwd)
 def _lstm_seq_fwd_range(pre, whh, c_all, hbuf, y, valid, k0, k1, static=None):
     ndir = len(pre)
     T, B, H4 = pre[0].shape
     H = H4 // 4
-    for d in range(ndir):
-        for t_, shp in ((pre[d], (T, B, 4 * H)), (whh[d], (4 * H, H)), (c_all[d], (T + 1, B, H)),
-                        (hbuf[d], (2, B, H))):
-            _chk(t_, 'lstm_seq tensor')
-            assert t_.is_contiguous() and tuple(t_.shape) == shp, (tuple(t_.shape), shp)
-    _chk(y, 'y'); _chk(valid, 'valid', torch.int64)
-    assert y.is_contiguous() and tuple(y.shape) == (T, B, ndir * H)
-    if static is not None:
-        assert len(static) == ndir
-        for t_ in static:
-            _chk(t_, 'static')
-            assert t_.is_contiguous() and tuple(t_.shape) == (B, 4 * H)
+    _check_table(_per_dir(ndir, (pre, 'pre', (T, B, 4 * H)), (whh, 'whh', (4 * H, H)), (c_all, 'c_all', (T + 1, B, H)),
+                          (hbuf, 'hbuf', (2, B, H)), (static, 'static', (B, 4 * H))) + [(y, 'y', (T, B, ndir * H))])
+    _chk(valid, 'valid', torch.int64)
     check(lib.ag_lstm_seq_fwd(_ptr_table(pre), _ptr_table(whh), _ptr_table(c_all), _ptr_table(hbuf), _p(y),
                               _p(valid), _ptr_table(static) if static is not None else None, T, B, H, ndir, k0, k1,
                               _stream()), 'ag_lstm_seq_fwd')
 
 
 def gfront_persist_ok(B, S, fs, dev):
-    return bool(PERSIST[0] and torch.device(dev).type == 'cuda' and lib.ag_gfront_persist_ok(B, S, fs, _n_cu(dev)))
-
-
-def _rows(t, name, B, n):
-    """row pitch of a [B, n] view with unit stride along dim 1 (a slab channel, a column block)"""
-    _chk(t, name)
-    assert t.dim() == 2 and tuple(t.shape) == (B, n) and (n == 1 or t.stride(1) == 1), (name, tuple(t.shape), t.stride())
-    return t.stride(0) if B > 1 else max(t.stride(0), n)
-
-
-_PITCHED = 'pitched'      # mark in a _front_check table: a 2-D view of unit stride along dim 1 and any row pitch
-
-
-def _front_check(table):
-    """the tensor checks of the fronts' persistent launches.  Rows (tensor, name, shape[, dtype or _PITCHED]): a device tensor
-    of that dtype (fp32 by default) and shape, dense unless marked _PITCHED (channel 0 of a slab, a column block of a
-    weight).  A tensor that is None (an optional one) is skipped.  Returns {name: row pitch} of the _PITCHED rows (0: None)"""
-    ld = {}
-    for t, name, shp, *kind in table:
-        if kind == [_PITCHED]:
-            ld[name] = _rows(t, name, *shp) if t is not None else 0
-        elif t is not None:
-            _chk(t, name, *kind)
-            assert t.is_contiguous() and tuple(t.shape) == shp, (name, tuple(t.shape), shp)
-    return ld
+    return _persist_ok(lib.ag_gfront_persist_ok, (B, S, fs), dev)
 
 
 def _front_launch(entry, args, dev, ws_bytes):
@@ -1250,13 +1292,21 @@ def _front_launch(entry, args, dev, ws_bytes):
     check(getattr(lib, entry)(C.byref(args), _stream()), entry)
 
 
+def _work_gfront(gates, wx, whh, wp, *a_, **kw):
+    T, B, S4 = gates.shape
+    S, fs = S4 // 4, wp.size(0)
+    return 'gfront_persist_fwd_kernel' + _bf16_tag(), T * 2.0 * B * (S4 * (S + fs) + fs * S), \
+        4.0 * (S4 * (S + fs) + fs * S + T * B * (2 * S4 + 2 * S + fs)), 1
+
+
+@_timed(_work_gfront)
 def gfront_fwd_persist(gates, wx, whh, wp, bp, hs, cs, x, xt=None):
     """the Generator front's frame loop in ONE persistent launch (ag_gfront_fwd, LSTM cell, training).  x: [B, T*fs] rows of
     any pitch (channel 0 of the conv trunk's slab); xt: optional [T,B,fs], receives the same frames time-major"""
     T, B, S4 = gates.shape
     S = S4 // 4
     fs = wp.size(0)
-    ld = _front_check(((gates, 'gates', (T, B, 4 * S)), (whh, 'whh', (4 * S, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
+    ld = _check_table(((gates, 'gates', (T, B, 4 * S)), (whh, 'whh', (4 * S, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
                        (hs, 'hs', (T, B, S)), (cs, 'cs', (T + 1, B, S)), (xt, 'xt', (T, B, fs)),
                        (x, 'x', (B, T * fs), _PITCHED), (wx, 'wx', (4 * S, fs), _PITCHED)))
     a = _lib.FrontFwdArgs(cell=0, gen=0, gates=_p(gates), w_x=_p(wx), ldwx=ld['wx'], w_hh=_p(whh), w_p=_p(wp), b_p=_p(bp),
@@ -1285,10 +1335,17 @@ class front_bwd_persist(object):
 
 
 def gfront_bwd_persist_ok(B, S, fs, dev):
-    return bool(PERSIST[0] and PERSIST_FRONT_BWD[0] and torch.device(dev).type == 'cuda'
-                and lib.ag_gfront_bwd_persist_ok(B, S, fs, _n_cu(dev)))
+    return _persist_ok(lib.ag_gfront_bwd_persist_ok, (B, S, fs), dev, PERSIST_FRONT_BWD[0])
 
 
+def _work_gfront_bwd(gates, cs, x, dh_ext, dx_ext, whh, wx, wp, *a_, **kw):
+    T, B, S4 = gates.shape
+    S, fs = S4 // 4, wp.size(0)
+    return 'gfront_persist_bwd_kernel' + _bf16_tag(), 2.0 * B * ((T - 1) * S4 * (S + fs) + T * fs * S), \
+        4.0 * (S4 * (S + fs) + fs * S + T * B * (2 * S4 + 2 * S + (S + fs) + 2 * fs)), 1
+
+
+@_timed(_work_gfront_bwd)
 def gfront_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, wx, wp, dgs, dxt):
     """the backward through time of the Generator front's frame loop in ONE persistent launch (ag_gfront_bwd, LSTM cell);
     the external gradients, read only, each may be None: dh_ext [T,B,S] = dL/dh_t (the stop head's), dx_ext [B,T*fs] rows of
@@ -1296,29 +1353,13 @@ def gfront_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, wx, wp, dgs, dxt):
     T, B, S4 = gates.shape
     S = S4 // 4
     fs = wp.size(0)
-    ld = _front_check(((gates, 'gates', (T, B, 4 * S)), (cs, 'cs', (T + 1, B, S)), (whh, 'whh', (4 * S, S)),
+    ld = _check_table(((gates, 'gates', (T, B, 4 * S)), (cs, 'cs', (T + 1, B, S)), (whh, 'whh', (4 * S, S)),
                        (wp, 'wp', (fs, S)), (dgs, 'dgs', (T, B, 4 * S)), (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)),
                        (x, 'x', (B, T * fs), _PITCHED), (dx_ext, 'dx_ext', (B, T * fs), _PITCHED),
                        (wx, 'wx', (4 * S, fs), _PITCHED)))
     a = _lib.FrontBwdArgs(cell=0, ga=_p(gates), state=_p(cs), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext), dx_ext=_p(dx_ext),
                           lddx=ld['dx_ext'], w_hh=_p(whh), w_x=_p(wx), ldwx=ld['wx'], w_p=_p(wp), dgs=_p(dgs), dxt=_p(dxt),
                           T=T, B=B, S=S, fs=fs)
-    _front_launch('ag_gfront_bwd', a, x.device, _PERSIST_WS_MIN)
-
-
-def grufront_bwd_persist(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, dgi, dgh, dxt):
-    """the GRU front's backward through time in ONE persistent launch (ag_gfront_bwd, GRU cell); hs [T+1,B,S] with
-    hs[t] = h_{t-1}; dh_ext / dx_ext: the external gradients as for gfront_bwd_persist"""
-    T, B, S3 = gates.shape
-    S = S3 // 3
-    fs = wp.size(0)
-    ld = _front_check(((gates, 'gates', (T, B, 3 * S)), (hs, 'hs', (T + 1, B, S)), (gh, 'gh', (T, B, 3 * S)),
-                       (whh, 'whh', (3 * S, S)), (wp, 'wp', (fs, S)), (dgi, 'dgi', (T, B, 3 * S)), (dgh, 'dgh', (T, B, 3 * S)),
-                       (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)), (x, 'x', (B, T * fs), _PITCHED),
-                       (dx_ext, 'dx_ext', (B, T * fs), _PITCHED), (wx, 'wx', (3 * S, fs), _PITCHED)))
-    a = _lib.FrontBwdArgs(cell=1, ga=_p(gates), state=_p(hs), gh=_p(gh), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext),
-                          dx_ext=_p(dx_ext), lddx=ld['dx_ext'], w_hh=_p(whh), w_x=_p(wx), ldwx=ld['wx'], w_p=_p(wp),
-                          dgs=_p(dgi), dgh=_p(dgh), dxt=_p(dxt), T=T, B=B, S=S, fs=fs)
     _front_launch('ag_gfront_bwd', a, x.device, _PERSIST_WS_MIN)
 
 
@@ -1329,13 +1370,38 @@ def _work_grufront_bwd(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, *a_, **kw)
         4.0 * (S3 * (S + fs) + fs * S + T * B * (4 * S3 + 2 * S + (S + fs) + 2 * fs)), 1
 
 
+@_timed(_work_grufront_bwd)
+def grufront_bwd_persist(gates, hs, gh, x, dh_ext, dx_ext, whh, wx, wp, dgi, dgh, dxt):
+    """the GRU front's backward through time in ONE persistent launch (ag_gfront_bwd, GRU cell); hs [T+1,B,S] with
+    hs[t] = h_{t-1}; dh_ext / dx_ext: the external gradients as for gfront_bwd_persist"""
+    T, B, S3 = gates.shape
+    S = S3 // 3
+    fs = wp.size(0)
+    ld = _check_table(((gates, 'gates', (T, B, 3 * S)), (hs, 'hs', (T + 1, B, S)), (gh, 'gh', (T, B, 3 * S)),
+                       (whh, 'whh', (3 * S, S)), (wp, 'wp', (fs, S)), (dgi, 'dgi', (T, B, 3 * S)), (dgh, 'dgh', (T, B, 3 * S)),
+                       (dxt, 'dxt', (T, B, fs)), (dh_ext, 'dh_ext', (T, B, S)), (x, 'x', (B, T * fs), _PITCHED),
+                       (dx_ext, 'dx_ext', (B, T * fs), _PITCHED), (wx, 'wx', (3 * S, fs), _PITCHED)))
+    a = _lib.FrontBwdArgs(cell=1, ga=_p(gates), state=_p(hs), gh=_p(gh), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext),
+                          dx_ext=_p(dx_ext), lddx=ld['dx_ext'], w_hh=_p(whh), w_x=_p(wx), ldwx=ld['wx'], w_p=_p(wp),
+                          dgs=_p(dgi), dgh=_p(dgh), dxt=_p(dxt), T=T, B=B, S=S, fs=fs)
+    _front_launch('ag_gfront_bwd', a, x.device, _PERSIST_WS_MIN)
+
+
+def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):
+    T, B, S3 = gates.shape
+    S, fs = S3 // 3, wp.size(0)
+    return 'gfront_persist_fwd_kernel<gru>', T * 2.0 * B * (S3 * (S + fs) + fs * S), \
+        4.0 * (S3 * (S + fs) + fs * S + T * B * (2 * S3 + 2 * S + fs)), 1
+
+
+@_timed(_work_grufront)
 def grufront_fwd_persist(gates, gh, wx, whh, bhn, wp, bp, hs, x, xt=None):
     """the GRU-front generator's frame loop in ONE persistent launch (ag_gfront_fwd, GRU cell, training); hs: [T,B,S] (h_t);
     x / xt as for gfront_fwd_persist"""
     T, B, S3 = gates.shape
     S = S3 // 3
     fs = wp.size(0)
-    ld = _front_check(((gates, 'gates', (T, B, 3 * S)), (gh, 'gh', (T, B, 3 * S)), (whh, 'whh', (3 * S, S)), (bhn, 'bhn', (S,)),
+    ld = _check_table(((gates, 'gates', (T, B, 3 * S)), (gh, 'gh', (T, B, 3 * S)), (whh, 'whh', (3 * S, S)), (bhn, 'bhn', (S,)),
                        (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)), (hs, 'hs', (T, B, S)), (xt, 'xt', (T, B, fs)),
                        (x, 'x', (B, T * fs), _PITCHED), (wx, 'wx', (3 * S, fs), _PITCHED)))
     a = _lib.FrontFwdArgs(cell=1, gen=0, gates=_p(gates), gh=_p(gh), w_x=_p(wx), ldwx=ld['wx'], w_hh=_p(whh), b_hn=_p(bhn),
@@ -1356,7 +1422,7 @@ def gfront_gen_persist(pre, wx, whh, wp, bp, ws, bs, u, x, s, first, t_run, bhn=
     assert SG == (3 if cell else 4) * S, (tuple(pre.shape), tuple(whh.shape))
     assert ws.numel() == S, tuple(ws.shape)
     bhn = bhn if cell else None
-    ld = _front_check(((pre, 'pre', (T, B, SG)), (whh, 'whh', (SG, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
+    ld = _check_table(((pre, 'pre', (T, B, SG)), (whh, 'whh', (SG, S)), (wp, 'wp', (fs, S)), (bp, 'bp', (fs,)),
                        (bs, 'bs', (1,)), (u, 'u', (T, B)), (bhn, 'bhn', (S,)), (ws, 'ws', tuple(ws.shape)),
                        (first, 'first', (B,), torch.int32), (t_run, 't_run', (1,), torch.int32),
                        (x, 'x', (B, T * fs), _PITCHED), (s, 's', (B, T), _PITCHED), (wx, 'wx', (SG, fs), _PITCHED)))
@@ -1371,8 +1437,7 @@ PERSIST_FRONT_STACK = [True]
 
 
 def gfront_stack_ok(B, S, fs, nl, dev):
-    return bool(PERSIST[0] and PERSIST_FRONT_STACK[0] and torch.device(dev).type == 'cuda'
-                and lib.ag_gfront_stack_ok(B, S, fs, nl, _n_cu(dev)))
+    return _persist_ok(lib.ag_gfront_stack_ok, (B, S, fs, nl), dev, PERSIST_FRONT_STACK[0])
 
 
 def _stack_tables(a, **tables):
@@ -1383,6 +1448,16 @@ def _stack_tables(a, **tables):
             arr[i] = _p(t)
 
 
+def _work_gfront_stack(gates, wx, w_in, whh, *a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S, fs = S4 // 4, wx.size(1)
+    return None, T * 2.0 * B * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S), \
+        4.0 * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + fs)), 1
+
+
+@_timed(_work_gfront_stack)
 def gfront_stack_fwd_persist(gates, wx, w_in, whh, bias, wp, bp, hs, cs, x, xt=None):
     """the frame loop of a STACKED LSTM front in ONE persistent launch (ag_gfront_stack_fwd, training).  Lists over the nl
     layers: gates [T,B,4S] (gates[0] holds the z / c pre-activations incl. both biases and, like the others, receives the
@@ -1400,7 +1475,7 @@ def gfront_stack_fwd_persist(gates, wx, w_in, whh, bias, wp, bp, hs, cs, x, xt=N
                  (hs[l], 'hs[%d]' % l, (T, B, S)), (cs[l], 'cs[%d]' % l, (T + 1, B, S))]
     for l in range(nl - 1):
         rows += [(w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)), (bias[l], 'bias[%d]' % (l + 1), (4 * S,))]
-    ld = _front_check(rows)
+    ld = _check_table(rows)
     a = _lib.FrontStackArgs(gen=0, nl=nl, ldwx=ld['wx'], w_p=_p(wp), b_p=_p(bp), x=_p(x), ldx=ld['x'], xt=_p(xt),
                             T=T, B=B, S=S, fs=fs)
     _stack_tables(a, gates=gates, hs=hs, cs=cs, w_hh=whh, w_in=[wx] + list(w_in), bias=[None] + list(bias))
@@ -1423,20 +1498,11 @@ def gfront_stack_gen_persist(pre, wx, w_in, whh, bias, wp, bp, ws, bs, u, x, s, 
         rows.append((whh[l], 'whh[%d]' % l, (4 * S, S)))
     for l in range(nl - 1):
         rows += [(w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)), (bias[l], 'bias[%d]' % (l + 1), (4 * S,))]
-    ld = _front_check(rows)
+    ld = _check_table(rows)
     a = _lib.FrontStackArgs(gen=1, nl=nl, ldwx=ld['wx'], w_p=_p(wp), b_p=_p(bp), w_s=_p(ws), b_s=_p(bs), u=_p(u), x=_p(x),
                             ldx=ld['x'], s=_p(s), lds=ld['s'], first=_p(first), t_run=_p(t_run), T=T, B=B, S=S, fs=fs)
     _stack_tables(a, gates=[pre], w_hh=whh, w_in=[wx] + list(w_in), bias=[None] + list(bias))
     _front_launch('ag_gfront_stack_fwd', a, x.device, int(lib.ag_gfront_stack_ws_bytes(B, S, fs, nl)))
-
-
-def _work_gfront_stack(gates, wx, w_in, whh, *a_, **kw):
-    """(filed under the name the launch site reported: ag_last_kernel)"""
-    nl = len(gates)
-    T, B, S4 = gates[0].shape
-    S, fs = S4 // 4, wx.size(1)
-    return None, T * 2.0 * B * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S), \
-        4.0 * (S4 * (S + fs) + (nl - 1) * S4 * 2 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + fs)), 1
 
 
 # the stacked front's backward through time in one persistent launch; off: one launch per operation and frame
@@ -1445,10 +1511,20 @@ PERSIST_FRONT_STACK_BWD = [True]
 
 def gfront_stack_bwd_ok(B, S, fs, nl, dev):
     """(PERSIST_FRONT_BWD: the multi-GPU rule of the one-layer backward holds for this launch too)"""
-    return bool(PERSIST[0] and PERSIST_FRONT_STACK[0] and PERSIST_FRONT_STACK_BWD[0] and PERSIST_FRONT_BWD[0]
-                and torch.device(dev).type == 'cuda' and lib.ag_gfront_stack_bwd_ok(B, S, fs, nl, _n_cu(dev)))
+    return _persist_ok(lib.ag_gfront_stack_bwd_ok, (B, S, fs, nl), dev,
+                       PERSIST_FRONT_STACK[0] and PERSIST_FRONT_STACK_BWD[0] and PERSIST_FRONT_BWD[0])
 
 
+def _work_gfront_stack_bwd(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, *a_, **kw):
+    """(filed under the name the launch site reported: ag_last_kernel)"""
+    nl = len(gates)
+    T, B, S4 = gates[0].shape
+    S, fs = S4 // 4, wp.size(0)
+    return None, 2.0 * B * ((T - 1) * S4 * (nl * S + fs) + T * ((nl - 1) * S4 * S + fs * S)), \
+        4.0 * (S4 * (nl * S + fs) + (nl - 1) * S4 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + S + 3 * fs)), 1
+
+
+@_timed(_work_gfront_stack_bwd)
 def gfront_stack_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, dgs, dxt):
     """the backward through time of a STACKED LSTM front in ONE persistent launch (ag_gfront_stack_bwd).  Lists over the nl
     layers: gates [T,B,4S] (activated), cs [T+1,B,S], whh [4S,S], dgs [T,B,4S] (out); w_in: W_ih_l [4S,S] of the layers from
@@ -1466,47 +1542,25 @@ def gfront_stack_bwd_persist(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, dg
                  (whh[l], 'whh[%d]' % l, (4 * S, S)), (dgs[l], 'dgs[%d]' % l, (T, B, 4 * S))]
     for l in range(nl - 1):
         rows.append((w_in[l], 'w_in[%d]' % (l + 1), (4 * S, S)))
-    ld = _front_check(rows)
+    ld = _check_table(rows)
     a = _lib.FrontStackBwdArgs(nl=nl, w_p=_p(wp), x=_p(x), ldx=ld['x'], dh_ext=_p(dh_ext), dx_ext=_p(dx_ext),
                                lddx=ld['dx_ext'], ldwx=ld['wx'], dxt=_p(dxt), T=T, B=B, S=S, fs=fs)
     _stack_tables(a, ga=gates, cs=cs, w_hh=whh, w_in=[wx] + list(w_in), dgs=dgs)
     _front_launch('ag_gfront_stack_bwd', a, x.device, int(lib.ag_gfront_stack_bwd_ws_bytes(B, S, fs, nl)))
 
 
-def _work_gfront_stack_bwd(gates, cs, x, dh_ext, dx_ext, whh, w_in, wx, wp, *a_, **kw):
-    """(filed under the name the launch site reported: ag_last_kernel)"""
-    nl = len(gates)
-    T, B, S4 = gates[0].shape
-    S, fs = S4 // 4, wp.size(0)
-    return None, 2.0 * B * ((T - 1) * S4 * (nl * S + fs) + T * ((nl - 1) * S4 * S + fs * S)), \
-        4.0 * (S4 * (nl * S + fs) + (nl - 1) * S4 * S + fs * S + T * B * (nl * (2 * S4 + 2 * S) + S + 3 * fs)), 1
-
-
-def _work_grufront(gates, gh, wx, whh, bhn, wp, *a_, **kw):
-    T, B, S3 = gates.shape
-    S, fs = S3 // 3, wp.size(0)
-    return 'gfront_persist_fwd_kernel<gru>', T * 2.0 * B * (S3 * (S + fs) + fs * S), \
-        4.0 * (S3 * (S + fs) + fs * S + T * B * (2 * S3 + 2 * S + fs)), 1
-
-
-def _work_gfront(gates, wx, whh, wp, *a_, **kw):
-    T, B, S4 = gates.shape
-    S, fs = S4 // 4, wp.size(0)
-    return 'gfront_persist_fwd_kernel' + _bf16_tag(), T * 2.0 * B * (S4 * (S + fs) + fs * S), \
-        4.0 * (S4 * (S + fs) + fs * S + T * B * (2 * S4 + 2 * S + fs)), 1
-
-
-def _work_gfront_bwd(gates, cs, x, dh_ext, dx_ext, whh, wx, wp, *a_, **kw):
-    T, B, S4 = gates.shape
-    S, fs = S4 // 4, wp.size(0)
-    return 'gfront_persist_bwd_kernel' + _bf16_tag(), 2.0 * B * ((T - 1) * S4 * (S + fs) + T * fs * S), \
-        4.0 * (S4 * (S + fs) + fs * S + T * B * (2 * S4 + 2 * S + (S + fs) + 2 * fs)), 1
-
-
 def lstm_persist_bwd_ok(B, H, ndir, dev):
-    return bool(PERSIST[0] and lib.ag_lstm_persist_bwd_ok(B, H, ndir, _n_cu(dev)))
+    return _persist_ok(lib.ag_lstm_persist_bwd_ok, (B, H, ndir), dev)
 
 
+def _work_seq_bwd_persist(gates, whh, c_all, dy, dgates, valid, dgsum=None, dg16=None):
+    T, B, H4 = gates[0].shape
+    nd = len(gates)
+    return 'lstm_persist_bwd_kernel' + _bf16_tag(), T * 2.0 * nd * B * H4 * (H4 // 4), \
+        4.0 * nd * (H4 * (H4 // 4) + T * 5.5 * B * H4), 1
+
+
+@_timed(_work_seq_bwd_persist)
 def _lstm_seq_bwd_persist_call(gates, whh, c_all, dy, dgates, valid, dgsum=None, dg16=None):
     """ONE persistent launch for the whole backward through time (ag_lstm_seq_bwd_persist); dgsum: optional list of
     [B,4H] outputs (one per direction) = the sum over time of dgates; dy: fp32 or bf16; dg16: optional list of [T,B,4H]
@@ -1514,18 +1568,10 @@ def _lstm_seq_bwd_persist_call(gates, whh, c_all, dy, dgates, valid, dgsum=None,
     ndir = len(gates)
     T, B, H4 = gates[0].shape
     H = H4 // 4
-    for d in range(ndir):
-        for t_, shp in ((gates[d], (T, B, 4 * H)), (whh[d], (4 * H, H)), (c_all[d], (T + 1, B, H)),
-                        (dgates[d], (T, B, 4 * H))):
-            _chk(t_, 'lstm_seq tensor')
-            assert t_.is_contiguous() and tuple(t_.shape) == shp, (tuple(t_.shape), shp)
-    _chk_any(dy, 'dy'); _chk(valid, 'valid', torch.int64)
-    assert dy.is_contiguous() and tuple(dy.shape) == (T, B, ndir * H)
-    if dgsum is not None:
-        assert len(dgsum) == ndir
-        for t_ in dgsum:
-            _chk(t_, 'dgsum')
-            assert t_.is_contiguous() and tuple(t_.shape) == (B, 4 * H)
+    _check_table(_per_dir(ndir, (gates, 'gates', (T, B, 4 * H)), (whh, 'whh', (4 * H, H)), (c_all, 'c_all', (T + 1, B, H)),
+                          (dgates, 'dgates', (T, B, 4 * H)), (dgsum, 'dgsum', (B, 4 * H)))
+                 + [(dy, 'dy', (T, B, ndir * H), _F32_OR_BF16)])
+    _chk(valid, 'valid', torch.int64)
     ld16 = 0
     if dg16 is not None:
         assert len(dg16) == ndir
@@ -1542,11 +1588,43 @@ def _lstm_seq_bwd_persist_call(gates, whh, c_all, dy, dgates, valid, dgsum=None,
           'ag_lstm_seq_bwd_persist')
 
 
-def _work_seq_bwd_persist(gates, whh, c_all, dy, dgates, valid, dgsum=None, dg16=None):
+def _lstm_seq_bwd_range(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, k0, k1, phases=3):
+    """steps k1 - 1 .. k0 of the per-step backward, one launch per step and phase (ag_lstm_seq_bwd; phases: 1 = the cell
+    backward, 2 = the recurrent product, 3 = both)"""
+    ndir = len(gates)
+    T, B, H4 = gates[0].shape
+    H = H4 // 4
+    _check_table(_per_dir(ndir, (gates, 'gates', (T, B, 4 * H)), (whh, 'whh', (4 * H, H)), (c_all, 'c_all', (T + 1, B, H)),
+                          (dgates, 'dgates', (T, B, 4 * H)), (dhbuf, 'dhbuf', (2, B, H)), (dcbuf, 'dcbuf', (2, B, H)))
+                 + [(dy, 'dy', (T, B, ndir * H))])
+    _chk(valid, 'valid', torch.int64)
+    _ws = _bind_ws(ndir * lib.ag_skinny_ws_numel(B, H, 4 * H), dy.device) if H % 16 else None  # noqa: F841
+    check(lib.ag_lstm_seq_bwd(_ptr_table(gates), _ptr_table(whh), _ptr_table(c_all), _p(dy),
+                              _ptr_table(dgates), _ptr_table(dhbuf), _ptr_table(dcbuf), _p(valid), T, B, H,
+                              ndir, k0, k1, phases, _stream()), 'ag_lstm_seq_bwd')
+
+
+# the same call under three names: what lstm_seq_bwd files its launches under when the Profiler is on
+def _work_seq_bwd_cell(gates, whh, *a_, **kw):
+    T, B, H4 = gates[0].shape
+    return 'lstm_cell_bwd2_kernel', 0.0, 4.0 * len(gates) * B * H4 * 3.5
+
+
+def _work_seq_bwd_prod(gates, whh, *a_, **kw):
     T, B, H4 = gates[0].shape
     nd = len(gates)
-    return 'lstm_persist_bwd_kernel' + _bf16_tag(), T * 2.0 * nd * B * H4 * (H4 // 4), \
-        4.0 * nd * (H4 * (H4 // 4) + T * 5.5 * B * H4), 1
+    return 'skinny_gemm_kernel', 2.0 * nd * B * H4 * (H4 // 4), 4.0 * nd * (H4 * (H4 // 4) + 2 * B * H4)
+
+
+def _work_seq_bwd_step(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, k0, k1, *a_, **kw):
+    T, B, H4 = gates[0].shape
+    nd, n = len(gates), k1 - k0
+    return 'lstm_step_bwd_kernel', n * 2.0 * nd * B * H4 * (H4 // 4), n * 4.0 * nd * (H4 * (H4 // 4) + 5.5 * B * H4), n
+
+
+_lstm_seq_bwd_cell = _timed(_work_seq_bwd_cell, name='_lstm_seq_bwd_cell')(_lstm_seq_bwd_range)
+_lstm_seq_bwd_prod = _timed(_work_seq_bwd_prod, name='_lstm_seq_bwd_prod')(_lstm_seq_bwd_range)
+_lstm_seq_bwd_step = _timed(_work_seq_bwd_step, name='_lstm_seq_bwd_step')(_lstm_seq_bwd_range)
 
 
 def lstm_seq_bwd(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, dgsum=None, dg16=None):
@@ -1573,91 +1651,10 @@ def lstm_seq_bwd(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, dgsum=None,
     return False
 
 
-def _lstm_seq_bwd_cell(*a):
-    _lstm_seq_bwd_range(*a)
-
-
-def _lstm_seq_bwd_prod(*a):
-    _lstm_seq_bwd_range(*a)
-
-
-def _lstm_seq_bwd_step(*a):
-    _lstm_seq_bwd_range(*a)
-
-
-def _lstm_seq_bwd_range(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, k0, k1, phases=3):
-    ndir = len(gates)
-    T, B, H4 = gates[0].shape
-    H = H4 // 4
-    for d in range(ndir):
-        for t_, shp in ((gates[d], (T, B, 4 * H)), (whh[d], (4 * H, H)), (c_all[d], (T + 1, B, H)),
-                        (dgates[d], (T, B, 4 * H)), (dhbuf[d], (2, B, H)), (dcbuf[d], (2, B, H))):
-            _chk(t_, 'lstm_seq tensor')
-            assert t_.is_contiguous() and tuple(t_.shape) == shp, (tuple(t_.shape), shp)
-    _chk(dy, 'dy'); _chk(valid, 'valid', torch.int64)
-    assert dy.is_contiguous() and tuple(dy.shape) == (T, B, ndir * H)
-    _ws = _bind_ws(ndir * lib.ag_skinny_ws_numel(B, H, 4 * H), dy.device) if H % 16 else None  # noqa: F841
-    check(lib.ag_lstm_seq_bwd(_ptr_table(gates), _ptr_table(whh), _ptr_table(c_all), _p(dy),
-                              _ptr_table(dgates), _ptr_table(dhbuf), _ptr_table(dcbuf), _p(valid), T, B, H,
-                              ndir, k0, k1, phases, _stream()), 'ag_lstm_seq_bwd')
-
-
-def _work_skinny(A, B, Cm, tb=False, *a_, **kw):
-    M, N = Cm.shape
-    return 'skinny_gemm_kernel', 2.0 * M * N * A.size(1), \
-        4.0 * (A.numel() + N * A.size(1) + M * N)
-
-
-def _work_step(gates_pre, x, wx, h_prev, whh, *a_, **kw):
-    B, H4 = gates_pre.shape
-    Kd = H4 // 4 + (x.size(1) if x is not None else 0)
-    return 'lstm_step_fwd_kernel', 2.0 * B * H4 * Kd, 4.0 * (H4 * Kd + 3 * B * H4)
-
-
-def _work_seq_fwd(pre, whh, c_all, hbuf, y, valid, k0, k1, *a_, **kw):
-    T, B, H4 = pre[0].shape
-    nd, n = len(pre), k1 - k0
-    return 'lstm_step_fwd_kernel', n * 2.0 * nd * B * H4 * (H4 // 4), n * 4.0 * nd * (H4 * (H4 // 4) + 3 * B * H4), n
-
-
-def _work_seq_fwd_persist(pre, whh, c_all, y, valid, static=None):
-    T, B, H4 = pre[0].shape
-    nd = len(pre)
-    # one launch = the whole layer pass: T steps of 2*B*4H*H flops per direction; algorithmic bytes: W_hh ONCE
-    # + gates in/out, cells, outputs per step
-    return 'lstm_persist_fwd_kernel' + _bf16_tag(), T * 2.0 * nd * B * H4 * (H4 // 4), \
-        4.0 * nd * (H4 * (H4 // 4) + T * 3 * B * H4), 1
-
-
-def _work_seq_bwd_prod(gates, whh, *a_, **kw):
-    T, B, H4 = gates[0].shape
-    nd = len(gates)
-    return 'skinny_gemm_kernel', 2.0 * nd * B * H4 * (H4 // 4), 4.0 * nd * (H4 * (H4 // 4) + 2 * B * H4)
-
-
-def _work_seq_bwd_step(gates, whh, c_all, dy, dgates, dhbuf, dcbuf, valid, k0, k1, *a_, **kw):
-    T, B, H4 = gates[0].shape
-    nd, n = len(gates), k1 - k0
-    return 'lstm_step_bwd_kernel', n * 2.0 * nd * B * H4 * (H4 // 4), n * 4.0 * nd * (H4 * (H4 // 4) + 5.5 * B * H4), n
-
-
-def _work_seq_bwd_cell(gates, whh, *a_, **kw):
-    T, B, H4 = gates[0].shape
-    return 'lstm_cell_bwd2_kernel', 0.0, 4.0 * len(gates) * B * H4 * 3.5
-
-
-for _n, _w in (('skinny_gemm', _work_skinny), ('lstm_step_fwd', _work_step),
-               ('_lstm_seq_fwd_range', _work_seq_fwd), ('_lstm_seq_fwd_persist_call', _work_seq_fwd_persist),
-               ('_lstm_seq_bwd_persist_call', _work_seq_bwd_persist), ('gfront_fwd_persist', _work_gfront), ('gfront_bwd_persist', _work_gfront_bwd), ('grufront_bwd_persist', _work_grufront_bwd),
-               ('grufront_fwd_persist', _work_grufront), ('gfront_stack_fwd_persist', _work_gfront_stack),
-               ('gfront_stack_bwd_persist', _work_gfront_stack_bwd),('_lstm_seq_bwd_prod', _work_seq_bwd_prod),
-               ('_lstm_seq_bwd_cell', _work_seq_bwd_cell), ('_lstm_seq_bwd_step', _work_seq_bwd_step)):
-    _instrument(_n, _w)
-
-
 # ------------------------------------------------------------------------------------
 # GRU cell pointwise (config C4)
 # ------------------------------------------------------------------------------------
+@_timed()
 def gru_cell_fwd(gi, gh, h_prev, h_out):
     """gi, gh: [B,3H] contiguous (complete products incl. biases); gi <- (r,z,n); h_out <- h'"""
     for t_, n in ((gi, 'gi'), (gh, 'gh')):
@@ -1670,6 +1667,7 @@ def gru_cell_fwd(gi, gh, h_prev, h_out):
                               B, H, _stream()), 'ag_gru_cell_fwd')
 
 
+@_timed()
 def gru_cell_bwd(gates_act, gh, h_prev, dh, dgi, dgh, dh_prev):
     for t_, n in ((gates_act, 'gates_act'), (gh, 'gh'), (dgi, 'dgi'), (dgh, 'dgh')):
         _chk(t_, n)
@@ -1681,20 +1679,13 @@ def gru_cell_bwd(gates_act, gh, h_prev, dh, dgi, dgh, dh_prev):
           'ag_gru_cell_bwd')
 
 
-for _n in ('gru_cell_fwd', 'gru_cell_bwd', 'rowdot_fwd', 'rowdot_bwd', 'build_zc', 'critic_batch', 'to_bf16'):
-    _instrument(_n, None)
-_instrument('gemm_h', _work_gemm_h)
-
-
+@_timed()
 def act_bwd2d(dy, y, dx, act, slope=LEAKY_SLOPE):
     """dx = dy * act'(.) on 2-D row-strided views (unit stride along dim 1)"""
     a, b, c = _mat(dy, 'dy'), _mat(y, 'y'), _mat(dx, 'dx')
     assert tuple(dy.shape) == tuple(y.shape) == tuple(dx.shape)
     check(lib.ag_act_bwd2d(_p(dy), a, _p(y), b, _p(dx), c, dy.size(0), dy.size(1), act, slope, _stream()),
           'ag_act_bwd2d')
-
-
-_instrument('act_bwd2d', None)
 
 
 # ------------------------------------------------------------------------------------
@@ -1704,6 +1695,7 @@ def conv_o1_ok(spec_kind, cout, K_, stride, pad):
     return spec_kind == 'conv' and cout == 1 and stride == 1 and K_ <= 9 and 2 * pad == K_ - 1
 
 
+@_timed()
 def conv_o1_fwd(x, w, bias, y, K_, pad, act=ACT_NONE, slope=LEAKY_SLOPE):
     """x [B,C,L] view, w [1,C,K] contiguous, y [B,1,L] view"""
     x_bs, x_cs = _bcl(x, 'x')
@@ -1715,6 +1707,7 @@ def conv_o1_fwd(x, w, bias, y, K_, pad, act=ACT_NONE, slope=LEAKY_SLOPE):
                                _stream()), 'ag_conv1d_o1_fwd')
 
 
+@_timed()
 def conv_o1_bwd_data(dy, w, dx, K_, pad, accumulate=False):
     dy_bs, _ = _bcl(dy, 'dy')
     dx_bs, dx_cs = _bcl(dx, 'dx')
@@ -1724,6 +1717,7 @@ def conv_o1_bwd_data(dy, w, dx, K_, pad, accumulate=False):
                                     int(accumulate), _stream()), 'ag_conv1d_o1_bwd_data')
 
 
+@_timed()
 def conv_o1_wgrad(dy, x, dw, K_, pad):
     dy_bs, _ = _bcl(dy, 'dy')
     x_bs, x_cs = _bcl(x, 'x')
@@ -1732,10 +1726,6 @@ def conv_o1_wgrad(dy, x, dw, K_, pad):
     _ws = _bind_ws(_SMALL_WS, dw.device)  # noqa: F841
     check(lib.ag_conv1d_o1_wgrad(_p(dy), dy_bs, _p(x), x_bs, x_cs, _p(dw), B, Cc, L, K_, pad, _stream()),
           'ag_conv1d_o1_wgrad')
-
-
-for _n in ('conv_o1_fwd', 'conv_o1_bwd_data', 'conv_o1_wgrad'):
-    _instrument(_n, None)
 
 
 # ------------------------------------------------------------------------------------
@@ -1784,6 +1774,7 @@ def _peep(t, name, H, F, W):
     return t
 
 
+@_timed()
 def convlstm_peephole_fwd(y, c, wci, wcf, j, ip, fp, o):
     H, B, F, W = c.shape
     _hbcw(y, 'y', (H, B, 4 * F, W))
@@ -1793,6 +1784,7 @@ def convlstm_peephole_fwd(y, c, wci, wcf, j, ip, fp, o):
                                        _p(ip), _p(fp), _p(o), H, B, F, W, _stream()), 'ag_convlstm_peephole_fwd')
 
 
+@_timed()
 def convlstm_peephole_bwd(dj, di, df, do, c, wci, wcf, dy, dc, dwci, dwcf):
     """dy [H,B,4F,W] written; dc accumulated into; dwci / dwcf written when given"""
     H, B, F, W = c.shape
@@ -1804,6 +1796,7 @@ def convlstm_peephole_bwd(dj, di, df, do, c, wci, wcf, dy, dc, dwci, dwcf):
                                        _p(_peep(dwcf, 'dw_cf', H, F, W)), H, B, F, W, _stream()), 'ag_convlstm_peephole_bwd')
 
 
+@_timed()
 def convlstm_cell_fwd(j, i_, f_, c, o_raw, wco, forget_bias, c_new, o_pre):
     H, B, F, W = c.shape
     for t_, n in ((j, 'j'), (i_, 'i'), (f_, 'f'), (c, 'c'), (o_raw, 'o_raw'), (c_new, 'c_new'), (o_pre, 'o_pre')):
@@ -1812,6 +1805,7 @@ def convlstm_cell_fwd(j, i_, f_, c, o_raw, wco, forget_bias, c_new, o_pre):
                                    _p(c_new), _p(o_pre), H, B, F, W, _stream()), 'ag_convlstm_cell_fwd')
 
 
+@_timed()
 def convlstm_cell_bwd(j, i_, f_, c, c_new, wco, forget_bias, dc_new, do_pre, dj, di, df, dc, dwco):
     """dc_new: in = dL/dc', out = dL/dc' + do_pre * W_co; dj, di, df, dc written; dwco written when given"""
     H, B, F, W = c.shape
@@ -1823,6 +1817,7 @@ def convlstm_cell_bwd(j, i_, f_, c, c_new, wco, forget_bias, dc_new, do_pre, dj,
                                    H, B, F, W, _stream()), 'ag_convlstm_cell_bwd')
 
 
+@_timed()
 def convlstm_out_fwd(o, c, h):
     for t_, n in ((o, 'o'), (c, 'c'), (h, 'h')):
         _chk(t_, n)
@@ -1830,6 +1825,7 @@ def convlstm_out_fwd(o, c, h):
     check(lib.ag_convlstm_out_fwd(_p(o), _p(c), _p(h), o.numel(), _stream()), 'ag_convlstm_out_fwd')
 
 
+@_timed()
 def convlstm_out_bwd(o, c, dh, do, dc):
     for t_, n in ((o, 'o'), (c, 'c'), (dh, 'dh'), (do, 'do'), (dc, 'dc')):
         _chk(t_, n)
@@ -1837,6 +1833,7 @@ def convlstm_out_bwd(o, c, dh, do, dc):
     check(lib.ag_convlstm_out_bwd(_p(o), _p(c), _p(dh), _p(do), _p(dc), o.numel(), _stream()), 'ag_convlstm_out_bwd')
 
 
+@_timed()
 def layer_norm_hbfw_fwd(x, gamma, beta, eps, y, mean, rstd):
     H, B, F, W = x.shape
     _hbcw(x, 'x'); _hbcw(y, 'y', x.shape)
@@ -1847,6 +1844,7 @@ def layer_norm_hbfw_fwd(x, gamma, beta, eps, y, mean, rstd):
           'ag_layer_norm_hbfw_fwd')
 
 
+@_timed()
 def layer_norm_hbfw_bwd(dy, x, gamma, mean, rstd, dx, dgp, dbp):
     H, B, F, W = x.shape
     _hbcw(x, 'x'); _hbcw(dy, 'dy', x.shape); _hbcw(dx, 'dx', x.shape)
@@ -1855,11 +1853,6 @@ def layer_norm_hbfw_bwd(dy, x, gamma, mean, rstd, dx, dgp, dbp):
         assert t_.is_contiguous() and t_.numel() == k, n
     check(lib.ag_layer_norm_hbfw_bwd(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgp), _p(dbp), H, B, F, W, _stream()),
           'ag_layer_norm_hbfw_bwd')
-
-
-for _n in ('convlstm_peephole_fwd', 'convlstm_peephole_bwd', 'convlstm_cell_fwd', 'convlstm_cell_bwd', 'convlstm_out_fwd',
-           'convlstm_out_bwd', 'layer_norm_hbfw_fwd', 'layer_norm_hbfw_bwd'):
-    _instrument(_n, None)
 
 
 # ------------------------------------------------------------------------------------
@@ -1876,6 +1869,7 @@ def _small_out(out, n, dev, name):
     return out
 
 
+@_timed(_work_named)
 def logit_summary(cls, nframes, positive, out=None):
     """one critic output cls [B,T'] (fp32, any strides: ``Discriminator.classify`` returns a transposed view) ->
     out [5] = (mean, std, hits, mask sum, hits / mask sum): mean / std over all B*T' entries, population (numpy's
@@ -1891,6 +1885,7 @@ def logit_summary(cls, nframes, positive, out=None):
     return out
 
 
+@_timed(_work_named)
 def sqnorm_rows(gx, nframes, scale, part=None, out=None, finish=True):
     """gx [B,L] (unit stride along L, any row pitch; 16-byte aligned rows are read four at a time) ->
     part[b] = scale * sum_l gx[b,l]^2 / nframes[b].  ``finish``: a second launch writes out[0] = mean_b part[b] (b ascending);
@@ -1908,6 +1903,7 @@ def sqnorm_rows(gx, nframes, scale, part=None, out=None, finish=True):
     return part, out
 
 
+@_timed(_work_named)
 def vec_stats(v, sign=1.0, out=None):
     """v [n] contiguous -> out [2] = (sign * mean(v), population std(v)) (ag_vec_stats; reward/mean, reward/std of :879-880)"""
     _chk(v, 'v')
@@ -1927,6 +1923,7 @@ def persist_status_word(dev):
     return lst[0][:4].view(torch.int32) if lst else None
 
 
+@_timed(_work_named)
 def summary_commit(ring, cursor, cols, part=None, part_col=-1):
     """one row of the summary ring in one launch (ag_summary_commit).  ring: int32 [capacity, 16] contiguous; cursor: int32
     [2] (next row, next sequence number; both advanced by the launch); cols: 16 entries, each a one-element float32 / int32
@@ -1961,15 +1958,6 @@ def summary_commit(ring, cursor, cols, part=None, part_col=-1):
     check(lib.ag_summary_commit(_p(tab), _stream()), 'ag_summary_commit')
 
 
-def _work_named(*a_, **kw):
-    """(filed under the name the launch site reported: ag_last_kernel)"""
-    return None, 0.0, 0.0
-
-
-for _n in ('logit_summary', 'sqnorm_rows', 'vec_stats', 'summary_commit'):
-    _instrument(_n, _work_named)
-
-
 # ------------------------------------------------------------------------------------
 # held-out evaluation (evaluate.Evaluator): long-term average spectrum of ragged clips, running critic statistics
 # ------------------------------------------------------------------------------------
@@ -1977,6 +1965,7 @@ LTAS_BINS = 129          # bins 0..128 of the 256-point DFT
 SCORE_WORDS = 6
 
 
+@_timed(_work_named)
 def ltas_power(x, lens, out=None, nframes=None):
     """x [B, L] (unit stride along L, any row pitch), lens int64 [B] or None -> out [B, 129] fp32: per clip the mean over its
     frames (256 samples, hop 128, periodic Hann; a clip shorter than one frame is ONE zero-padded frame) of the power
@@ -1997,6 +1986,7 @@ def ltas_power(x, lens, out=None, nframes=None):
     return out
 
 
+@_timed(_work_named)
 def score_accum(cls, nframes, target, positive, acc):
     """one critic output cls [B, T'] (fp32, any strides) ADDED to ``acc``, six float64 device words the caller zeroes once per
     evaluation: clips with a valid frame, sum_b of the per-clip mean BCE towards ``target``, valid frames, hits among them
@@ -2010,10 +2000,6 @@ def score_accum(cls, nframes, target, positive, acc):
     check(lib.ag_score_accum(_p(cls), cls.stride(0), cls.stride(1), _p(nframes), float(target), int(bool(positive)), _p(acc),
                              B, T, _stream()), 'ag_score_accum')
     return acc
-
-
-for _n in ('ltas_power', 'score_accum'):
-    _instrument(_n, _work_named)
 
 
 # ------------------------------------------------------------------------------------
@@ -2063,6 +2049,7 @@ def dct_table(bands=MEL_BANDS, ncep=MEL_NCEP, device='cuda'):
     return _align_table(('dct', int(bands), int(ncep)), lambda: _dct64(int(bands), int(ncep)), device)
 
 
+@_timed(_work_named)
 def melcep_frames(x, lens, mel=None, dct=None, cep=None, nframes=None, power=None):
     """x [B, L] and lens as ``ltas_power`` takes them -> cep [B, F, 16] fp32, F = lt_frames(L): per frame (256 samples, hop 128,
     periodic Hann) the 13 mel cepstra c[q] = sum_m dct[q, m] log(sum_k mel[m, k] |X[k]|^2 + 1e-10) in columns 0..12, zeros
@@ -2092,6 +2079,7 @@ def melcep_frames(x, lens, mel=None, dct=None, cep=None, nframes=None, power=Non
     return cep
 
 
+@_timed(_work_named)
 def dtw_cost(cep_a, nf_a, cep_b, nf_b, out=None):
     """cep_a [B, Fa, 16], cep_b [B, Fb, 16] (``melcep_frames`` rows), nf_a / nf_b int32 [B] -> out [B] fp32: the total of the
     symmetric dynamic-time-warping recursion D(i, j) = min(D(i-1, j) + d, D(i, j-1) + d, D(i-1, j-1) + 2 d), D(0, 0) = 2 d,
@@ -2111,6 +2099,7 @@ def dtw_cost(cep_a, nf_a, cep_b, nf_b, out=None):
     return out
 
 
+@_timed(_work_named)
 def dtw_pairs(cep_a, nf_a, cep_b, nf_b, ia=None, ib=None, out=None):
     """cep_a [Na, Fa, 16], cep_b [Nb, Fb, 16] (``melcep_frames`` rows), nf_a [Na] / nf_b [Nb] int32: two BANKS of sequences.
     ``ia``, ``ib`` (int32 [P], both or neither) -> out [P] fp32, out[p] = the ``dtw_cost`` total of a[ia[p]] against b[ib[p]]
@@ -2141,10 +2130,6 @@ def dtw_pairs(cep_a, nf_a, cep_b, nf_b, ia=None, ib=None, out=None):
     return out
 
 
-for _n in ('melcep_frames', 'dtw_cost', 'dtw_pairs'):
-    _instrument(_n, _work_named)
-
-
 # ------------------------------------------------------------------------------------
 # ingestion (audio.resample, ingest.build_store): polyphase resampling of ragged rows of PCM frames
 # ------------------------------------------------------------------------------------
@@ -2153,6 +2138,7 @@ def resample_ok(L, M, taps, channels, kind):
     return bool(lib.ag_resample_ok(int(L), int(M), int(taps), int(channels), int(kind)))
 
 
+@_timed(_work_named)
 def resample_poly(src, src_len, bank, L, M, dst=None, n_out=None, in_start=0, out_start=0):
     """src [B, n_in] or [B, n_in, C] (fp32 or int16; unit stride along the channels, C along the frames, any row pitch):
     frames in_start .. in_start + len_b - 1 of B signals, len_b = clamp(src_len[b], 0, n_in) (int64 [B] or None: n_in);
@@ -2187,10 +2173,6 @@ def resample_poly(src, src_len, bank, L, M, dst=None, n_out=None, in_start=0, ou
     return dst, counts
 
 
-for _n in ('resample_poly',):
-    _instrument(_n, _work_named)
-
-
 # ------------------------------------------------------------------------------------
 # the device-resident word store (dataset.DeviceWordStore, dataset.ClipBatch): clip facts once, one gather per minibatch
 # ------------------------------------------------------------------------------------
@@ -2205,6 +2187,7 @@ def _clip_store(bank, start, cap_or_n, second):
     return nc
 
 
+@_timed(_work_named)
 def clip_facts(bank, start, cap):
     """the packed store ``bank`` (fp32, clip c = bank[start[c] : start[c] + cap[c]], every start a multiple of 4 floats;
     ``start`` int64, ``cap`` int32) -> (n int32 [n_clips], peak fp32 [n_clips]): n = the index after the last sample that
@@ -2217,6 +2200,7 @@ def clip_facts(bank, start, cap):
     return n, peak
 
 
+@_timed(_work_named)
 def clip_gather(bank, start, n, peak, ids, out, len_out=None, frame=0):
     """``ids`` int64 [B] on the device, every one a clip of the store (the CALLER's duty: ``dataset.ClipBatch`` checks them on
     the host); ``out`` fp32 [B, W], unit stride along W, any row pitch and alignment; ``len_out`` int64 [B] or None.
@@ -2241,10 +2225,6 @@ def clip_gather(bank, start, n, peak, ids, out, len_out=None, frame=0):
     return out, len_out
 
 
-for _n in ('clip_facts', 'clip_gather'):
-    _instrument(_n, _work_named)
-
-
 # ------------------------------------------------------------------------------------
 # activity detection (audio.activity, ingest.build_store(trim / split)): frame power of ragged rows, runs of active frames
 # ------------------------------------------------------------------------------------
@@ -2262,6 +2242,7 @@ def frame_power_tile(win, hop):
     return int(lib.ag_frame_power_tile(int(win), int(hop)))
 
 
+@_timed(_work_named)
 def frame_power(src, src_len, win, hop, dst=None, n_frames=None, in_start=0, f_start=0):
     """src [B, n_in] fp32 (unit stride along the samples, any row pitch and alignment): samples in_start .. in_start + len_b - 1
     of B signals, len_b = clamp(src_len[b], 0, n_in) (int64 [B] or None: n_in), zero elsewhere.  -> dst [B, n_frames] fp32:
@@ -2284,6 +2265,7 @@ def frame_power(src, src_len, win, hop, dst=None, n_frames=None, in_start=0, f_s
     return dst
 
 
+@_timed(_work_named)
 def activity_segments(power, nf, lens, ratio, floor, min_gap, min_run, pad, win, hop, K=256, seg=None):
     """power [B, F] fp32 (unit stride along F, any row pitch), nf int32 [B] (<= F), lens int64 [B] -> (seg int64 [B, K, 2],
     count int32 [B], pmax fp32 [B]): the rule of the header - threshold max(pmax ratio, floor), gaps shorter than ``min_gap``
@@ -2308,5 +2290,3 @@ def activity_segments(power, nf, lens, ratio, floor, min_gap, min_run, pad, win,
     return seg, count, pmax
 
 
-for _n in ('frame_power', 'activity_segments'):
-    _instrument(_n, _work_named)

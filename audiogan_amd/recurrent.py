@@ -303,6 +303,12 @@ def _ext_grads(ds_tb, sw, dx, T, B, S):
     return dh_ext, dx if (dx is None or dx.stride(1) == 1) else dx.contiguous()
 
 
+def _one_launch(ok, T, wx, *dims):
+    """is a front's frame loop ONE persistent launch?  A frame to run, wx = W_ih[:, :fs] of unit stride along its rows, and
+    the launch's predicate: ``ok`` is a K.*_ok, looked up on K by the caller at call time, ``dims`` its arguments"""
+    return T > 0 and wx.stride(1) == 1 and ok(*dims)
+
+
 def _xprev_rows(x, xt, T, B, fs):
     """x_{t-1} for t = 1..T-1 as rows in (t, b) order, the operand of the W_ih[:, :fs] gradient: the persistent forward left
     the frames time-major (xt); otherwise a transposed copy of x [B, T*fs]"""
@@ -338,51 +344,22 @@ class GFrontFn(torch.autograd.Function):
         gates = [torch.empty(T, B, 4 * S, device=dev) for _ in range(nl)]
         hs = [torch.empty(T, B, S, device=dev) for _ in range(nl)]
         cs = [torch.empty(T + 1, B, S, device=dev) for _ in range(nl)]
-        w_ih0 = lw[0][0]
-        wx, wz = w_ih0[:, :fs], w_ih0[:, fs:]
+        wx, wz = lw[0][0][:, :fs], lw[0][0][:, fs:]
         _front_pre(zc, wz, lw[0][2], lw[0][3], gates[0], gru=False)
-        fused0 = K.lstm_step_ok(B, S, x[:, :fs], wx)
-        persist = nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev)
-        stack = nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_ok(B, S, fs, nl, dev)
         xt = None
-        if stack:
-            # the whole frame loop of ALL layers (every LSTMCell step + projection, fed back) in ONE launch; the history of
-            # every layer is written as the per-frame path below writes it, which is what the backward reads: one launch as
-            # well where K.gfront_stack_bwd_ok holds (ag_gfront_stack_bwd), the per-frame chain otherwise
+        if nl > 1 and _one_launch(K.gfront_stack_ok, T, wx, B, S, fs, nl, dev):
+            # the whole frame loop of ALL layers (every LSTMCell step + projection, fed back) in ONE launch; it writes every
+            # layer's history as the per-frame path does: the backward (one launch or the per-frame chain) reads either
             xt = torch.empty(T, B, fs, device=dev)
             K.gfront_stack_fwd_persist(gates, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
                                        [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, hs, cs, x, xt)
-            persist = True      # (nothing below but the stop head is left to do)
-        elif not persist:
-            for l in range(nl):
-                cs[l][0].zero_()                       # (the persistent launches write c_0 = 0 themselves)
-        h0 = None if persist else torch.zeros(B, S, device=dev)      # (only the per-frame path reads it)
-        bsum = None if persist else [lw[l][2] + lw[l][3] for l in range(nl)]
-        if persist and not stack:
+        elif nl == 1 and _one_launch(K.gfront_persist_ok, T, wx, B, S, fs, dev):
             # the whole frame loop (LSTMCell step + projection, fed back) in ONE launch, weights resident in registers; the
             # frames are also written time-major (xt): what the weight gradient of W_ih[:, :fs] reads in backward
             xt = torch.empty(T, B, fs, device=dev)
             K.gfront_fwd_persist(gates[0], wx, lw[0][1], pw, pb, hs[0], cs[0], x, xt)
-        for t in range(0 if persist else T):
-            xprev = x[:, (t - 1) * fs:t * fs] if t > 0 else x[:, :fs]
-            if fused0:
-                K.lstm_step_fwd(gates[0][t], xprev, wx, hs[0][t - 1] if t > 0 else h0, lw[0][1], cs[0][t],
-                                cs[0][t + 1], hs[0][t], first_step=(t == 0))
-            else:
-                if t > 0:
-                    K.gemm(xprev, wx, gates[0][t], tb=True, beta=1.0)
-                    K.gemm(hs[0][t - 1], lw[0][1], gates[0][t], tb=True, beta=1.0)
-                K.lstm_cell_fwd(gates[0][t], cs[0][t], cs[0][t + 1], h_out=hs[0][t])
-            for l in range(1, nl):
-                _small(hs[l - 1][t], lw[l][0], gates[l][t], tb=True, bias=bsum[l])
-                if K.lstm_step_ok(B, S):
-                    K.lstm_step_fwd(gates[l][t], None, None, hs[l][t - 1] if t > 0 else h0, lw[l][1],
-                                    cs[l][t], cs[l][t + 1], hs[l][t], first_step=(t == 0))
-                else:
-                    if t > 0:
-                        K.gemm(hs[l][t - 1], lw[l][1], gates[l][t], tb=True, beta=1.0)
-                    K.lstm_cell_fwd(gates[l][t], cs[l][t], cs[l][t + 1], h_out=hs[l][t])
-            _small(hs[-1][t], pw, x[:, t * fs:(t + 1) * fs], tb=True, bias=pb, act=ACT_TANH)
+        else:
+            GFrontFn._fwd_frames(T, B, fs, S, nl, x, gates, hs, cs, lw, wx, pw, pb)
         s = torch.empty(T * B, 1, device=dev)
         _linear1(hs[-1].view(T * B, S), sw, sb, s)
         ctx.front, ctx.key = front, front.group._key[1:]
@@ -390,6 +367,30 @@ class GFrontFn(torch.autograd.Function):
         ctx.has_xt = xt is not None
         ctx.save_for_backward(zc, x, *(gates + hs + cs + ([xt] if xt is not None else [])))
         return x, s.view(T, B).t()
+
+    @staticmethod
+    def _fwd_frames(T, B, fs, S, nl, x, gates, hs, cs, lw, wx, pw, pb):
+        """per-frame chain, one launch per operation (any number of layers); gates[0] holds the z / c pre-activations"""
+        fused = [K.lstm_step_ok(B, S, x[:, :fs], wx)] + [K.lstm_step_ok(B, S)] * (nl - 1)
+        for l in range(nl):
+            cs[l][0].zero_()                       # (the persistent launches write c_0 = 0 themselves)
+        h0 = torch.zeros(B, S, device=x.device)
+        bsum = [lw[l][2] + lw[l][3] for l in range(nl)]
+        for t in range(T):
+            xprev = x[:, (t - 1) * fs:t * fs] if t > 0 else x[:, :fs]
+            for l in range(nl):         # layer 0 reads the fed-back frame, the others the layer below
+                if l > 0:
+                    _small(hs[l - 1][t], lw[l][0], gates[l][t], tb=True, bias=bsum[l])
+                if fused[l]:
+                    K.lstm_step_fwd(gates[l][t], xprev if l == 0 else None, wx if l == 0 else None,
+                                    hs[l][t - 1] if t > 0 else h0, lw[l][1], cs[l][t], cs[l][t + 1], hs[l][t], first_step=t == 0)
+                else:
+                    if t > 0 and l == 0:
+                        K.gemm(xprev, wx, gates[0][t], tb=True, beta=1.0)
+                    if t > 0:
+                        K.gemm(hs[l][t - 1], lw[l][1], gates[l][t], tb=True, beta=1.0)
+                    K.lstm_cell_fwd(gates[l][t], cs[l][t], cs[l][t + 1], h_out=hs[l][t])
+            _small(hs[-1][t], pw, x[:, t * fs:(t + 1) * fs], tb=True, bias=pb, act=ACT_TANH)
 
     @staticmethod
     def _bwd_frames(T, B, fs, S, nl, x, dx, ds, gates, cs, lw, wx, pw, sw, hs, dws):
@@ -422,13 +423,12 @@ class GFrontFn(torch.autograd.Function):
         return dgs, dxt
 
     @staticmethod
-    def _bwd_frames_fused(T, B, fs, S, x, dx, ds, gates, cs, w_hh, wx, pw, sw, hs, dws, nl):
-        """single-layer front: ONE persistent launch where the shape fits (ag_gfront_bwd), else TWO launches per
-        frame: dacc[t] = [dL/dh_t | dL/dx_t] lives in one [B, S+fs] row so that  dacc[t-1] += dgates_t @ [W_hh |
+    def _bwd_frames_fused(T, B, fs, S, x, dx, ds, gates, cs, w_hh, wx, pw, sw, hs, dws, nl, persist):
+        """single-layer front: ONE persistent launch where the shape fits (``persist``: ag_gfront_bwd), else TWO launches
+        per frame: dacc[t] = [dL/dh_t | dL/dx_t] lives in one [B, S+fs] row so that  dacc[t-1] += dgates_t @ [W_hh |
         W_ih[:, :fs]]  is ONE product, and the tanh backward of the projection, its product and the cell backward are one
         fused step (ag_lstm_front_bwd_step)."""
         dev = x.device
-        persist = T > 0 and wx.stride(1) == 1 and K.gfront_bwd_persist_ok(B, S, fs, dev)
         ds_tb = _stop_head_grads(ds, hs.view(T * B, S), dws, 4 * nl + 2, defer=False) if ds is not None else None
         dgs = torch.empty(T, B, 4 * S, device=dev)
         dxt = torch.empty(T, B, fs, device=dev)
@@ -480,15 +480,12 @@ class GFrontFn(torch.autograd.Function):
             return (None, None) + tuple(front.group.backward(dws))
         dws = front.group.zero_dws() if wg else None
         # (the persistent launch takes frame sizes the fused per-frame step does not: any multiple of 8 up to its panel width)
-        fused = nl == 1 and T > 0 and (
-            (wx.stride(1) == 1 and K.gfront_bwd_persist_ok(B, S, fs, dev))
-            or ((S + fs) % 4 == 0 and K.lstm_front_bwd_ok(B, S, fs, x[:, :fs], x[:, :fs])
-                and K.skinny_ok(gates[0][0], lw[0][1], False)))
-        stack = nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_bwd_ok(B, S, fs, nl, dev)
-        if fused:
+        persist = nl == 1 and _one_launch(K.gfront_bwd_persist_ok, T, wx, B, S, fs, dev)
+        if persist or (nl == 1 and T > 0 and (S + fs) % 4 == 0 and K.lstm_front_bwd_ok(B, S, fs, x[:, :fs], x[:, :fs])
+                       and K.skinny_ok(gates[0][0], lw[0][1], False)):
             dgs, dxt = GFrontFn._bwd_frames_fused(T, B, fs, S, x, dx, ds, gates[0], cs[0], lw[0][1], wx, pw, sw,
-                                                  hs[0], dws, nl)
-        elif stack:
+                                                  hs[0], dws, nl, persist)
+        elif nl > 1 and _one_launch(K.gfront_stack_bwd_ok, T, wx, B, S, fs, nl, dev):
             # the whole loop of ALL layers in ONE launch (ag_gfront_stack_bwd); the stop head's gradient lands on the top layer
             ds_tb = _stop_head_grads(ds, hs[-1].view(T * B, S), dws, 4 * nl + 2, defer=False) if ds is not None else None
             dh_ext, dx_ext = _ext_grads(ds_tb, sw, dx, T, B, S)
@@ -560,26 +557,49 @@ class GRUFrontFn(torch.autograd.Function):
         gh = torch.empty(T, B, 3 * S, device=dev)      # h-part incl. b_hh (n slot needed for backward)
         hs = torch.empty(T + 1, B, S, device=dev)      # hs[t+1] = h_t, hs[0] = 0
         hs[0].zero_()
-        persist = T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev)
-        if persist:
+        if _one_launch(K.gfront_persist_ok, T, wx, B, S, fs, dev):
             # the whole frame loop (GRU step + projection, fed back) in ONE launch, weights resident in registers
             _front_pre(zc, wz, b_ih, b_hh, gi, gru=True)
             xt = torch.empty(T, B, fs, device=dev)
             K.grufront_fwd_persist(gi, gh, wx, w_hh, b_hh[2 * S:].contiguous(), pw, pb, hs[1:], x, xt)
         else:
-            K.gemm(zc.contiguous().view(T * B, Fz), wz, gi.view(T * B, 3 * S), tb=True, bias=b_ih)
-        for t in range(0 if persist else T):
-            if t > 0:
-                _small_acc(x[:, (t - 1) * fs:t * fs], wx, gi[t], tb=True)
-            _small(hs[t], w_hh, gh[t], tb=True, bias=b_hh)
-            K.gru_cell_fwd(gi[t], gh[t], hs[t], hs[t + 1])
-            _small(hs[t + 1], pw, x[:, t * fs:(t + 1) * fs], tb=True, bias=pb, act=ACT_TANH)
+            GRUFrontFn._fwd_frames(T, B, fs, S, zc, x, gi, gh, hs, wx, wz, w_hh, b_ih, b_hh, pw, pb)
         s = torch.empty(T * B, 1, device=dev)
         _linear1(hs[1:].view(T * B, S), sw, sb, s)
         ctx.front, ctx.key, ctx.dims = front, front.group._key[1:], (T, B, Fz)
         ctx.has_xt = xt is not None
         ctx.save_for_backward(zc, x, gi, gh, hs, *([xt] if xt is not None else []))
         return x, s.view(T, B).t()
+
+    @staticmethod
+    def _fwd_frames(T, B, fs, S, zc, x, gi, gh, hs, wx, wz, w_hh, b_ih, b_hh, pw, pb):
+        """per-frame chain, one launch per operation; hs[0] = 0 is the caller's"""
+        K.gemm(zc.contiguous().view(T * B, zc.size(2)), wz, gi.view(T * B, 3 * S), tb=True, bias=b_ih)
+        for t in range(T):
+            if t > 0:
+                _small_acc(x[:, (t - 1) * fs:t * fs], wx, gi[t], tb=True)
+            _small(hs[t], w_hh, gh[t], tb=True, bias=b_hh)
+            K.gru_cell_fwd(gi[t], gh[t], hs[t], hs[t + 1])
+            _small(hs[t + 1], pw, x[:, t * fs:(t + 1) * fs], tb=True, bias=pb, act=ACT_TANH)
+
+    @staticmethod
+    def _bwd_frames(T, B, fs, S, x, dx, ds_tb, gi, gh, hs, w_hh, wx, pw, sw, dgi, dgh, dxt):
+        """per-frame chain, one launch per operation, into dgi, dgh and dxt"""
+        dev = x.device
+        dxa = dx.contiguous().clone() if dx is not None else torch.zeros(B, T * fs, device=dev)
+        dha = torch.zeros(T + 1, B, S, device=dev)     # dha[t+1] accumulates dL/dh_t
+        if ds_tb is not None:
+            K.gemm(ds_tb, sw, dha[1:].view(T * B, S))
+        dh_dir = torch.empty(B, S, device=dev)
+        for t in reversed(range(T)):
+            gx = dxt[t]
+            K.act_bwd2d(dxa[:, t * fs:(t + 1) * fs], x[:, t * fs:(t + 1) * fs], gx, ACT_TANH)
+            _small_acc(gx, pw, dha[t + 1])
+            K.gru_cell_bwd(gi[t], gh[t], hs[t], dha[t + 1], dgi[t], dgh[t], dh_dir)
+            K.axpby(dh_dir, dha[t], 1.0, 1.0)                     # direct path  dh * z
+            _small_acc(dgh[t], w_hh, dha[t])                      # through the hidden product
+            if t > 0:
+                _small_acc(dgi[t], wx, dxa[:, (t - 1) * fs:t * fs])
 
     @staticmethod
     def backward(ctx, dx, ds):
@@ -595,30 +615,16 @@ class GRUFrontFn(torch.autograd.Function):
         dev = zc.device
         wg = any(ctx.needs_input_grad[2:])
         dws = front.group.zero_dws() if wg else None
-        persist = T > 0 and K.gfront_bwd_persist_ok(B, S, fs, dev) and wx.stride(1) == 1
         dgi = torch.empty(T, B, 3 * S, device=dev)
         dgh = torch.empty(T, B, 3 * S, device=dev)
         dxt = torch.empty(T, B, fs, device=dev)
         ds_tb = _stop_head_grads(ds, hs[1:].view(T * B, S), dws, 6, defer=False) if ds is not None else None
-        if persist:
+        if _one_launch(K.gfront_bwd_persist_ok, T, wx, B, S, fs, dev):
             # the whole loop in ONE launch (ag_gfront_bwd)
             dh_ext, dx_ext = _ext_grads(ds_tb, sw, dx, T, B, S)
             K.grufront_bwd_persist(gi, hs, gh, x, dh_ext, dx_ext, w_hh, wx, pw, dgi, dgh, dxt)
         else:
-            dxa = dx.contiguous().clone() if dx is not None else torch.zeros(B, T * fs, device=dev)
-            dha = torch.zeros(T + 1, B, S, device=dev)     # dha[t+1] accumulates dL/dh_t
-            if ds_tb is not None:
-                K.gemm(ds_tb, sw, dha[1:].view(T * B, S))
-            dh_dir = torch.empty(B, S, device=dev)
-        for t in reversed(range(0 if persist else T)):
-            gx = dxt[t]
-            K.act_bwd2d(dxa[:, t * fs:(t + 1) * fs], x[:, t * fs:(t + 1) * fs], gx, ACT_TANH)
-            _small_acc(gx, pw, dha[t + 1])
-            K.gru_cell_bwd(gi[t], gh[t], hs[t], dha[t + 1], dgi[t], dgh[t], dh_dir)
-            K.axpby(dh_dir, dha[t], 1.0, 1.0)                     # direct path  dh * z
-            _small_acc(dgh[t], w_hh, dha[t])                      # through the hidden product
-            if t > 0:
-                _small_acc(dgi[t], wx, dxa[:, (t - 1) * fs:t * fs])
+            GRUFrontFn._bwd_frames(T, B, fs, S, x, dx, ds_tb, gi, gh, hs, w_hh, wx, pw, sw, dgi, dgh, dxt)
         dxt2, dgi2, dgh2 = dxt.view(T * B, fs), dgi.view(T * B, 3 * S), dgh.view(T * B, 3 * S)
         if wg:
             K.gemm(dxt2, hs[1:].view(T * B, S), dws[4], ta=True)
@@ -651,10 +657,9 @@ def front_sample(front, zc, u):
     t when u[t,b] < sigmoid(s[b,t]) (the reference's Bernoulli draw, :450).  Returns (x [B, T*fs], s [B,T], first int64 [B])
     where first[b] = the frames clip b generates; only the first max(first) frames of x and s are meaningful.
 
-    Where a persistent launch fits (one layer: ag_gfront_fwd at a supported (B, S, fs); 2 to 8 LSTM layers:
-    ag_gfront_stack_fwd at a supported (B, S, fs, nl)): ONE launch (gen = 1), which draws the
-    stops itself, keeps no history and leaves its frame loop one frame after every clip has stopped.  Otherwise the training
-    front runs over all T frames under no_grad and the same rule is applied to its logits."""
+    Where a persistent launch fits (one layer: ag_gfront_fwd at a supported (B, S, fs); 2 to 8 LSTM layers: ag_gfront_stack_fwd
+    at a supported (B, S, fs, nl)): ONE launch (gen = 1), which draws the stops itself, keeps no history and leaves its frame
+    loop one frame after every clip has stopped.  Otherwise the training front runs under no_grad, same rule on its logits."""
     T, B, Fz = zc.shape
     fs, S = front.fs, front.ss
     gru = isinstance(front, GRUFront)
@@ -664,30 +669,24 @@ def front_sample(front, zc, u):
     w_ih, w_hh, b_ih, b_hh = [p_.w for p_ in prep[:4]]
     pw, pb, sw, sb = [p_.w for p_ in prep[4 * nl:4 * nl + 4]]
     wx, wz = w_ih[:, :fs], w_ih[:, fs:]
-    if nl > 1 and T > 0 and wx.stride(1) == 1 and K.gfront_stack_ok(B, S, fs, nl, dev):
-        # a stacked front: ONE ag_gfront_stack_fwd launch (gen = 1); the top layer's h feeds the projection and the stop head
-        lw = [[p_.w for p_ in prep[4 * l:4 * l + 4]] for l in range(nl)]
-        pre = torch.empty(T, B, 4 * S, device=dev)
-        _front_pre(zc, wz, b_ih, b_hh, pre, False)
-        x = _frames_buffer(front, B, T * fs, dev)
-        s = torch.empty(B, T, device=dev)
-        first = torch.empty(B, dtype=torch.int32, device=dev)
-        t_run = torch.empty(1, dtype=torch.int32, device=dev)
-        K.gfront_stack_gen_persist(pre, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
-                                   [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, sw.view(-1), sb, u.contiguous(),
-                                   x, s, first, t_run)
-        return x, s, first.long(), t_run
-    if nl == 1 and T > 0 and wx.stride(1) == 1 and K.gfront_persist_ok(B, S, fs, dev):
+    stack = nl > 1 and _one_launch(K.gfront_stack_ok, T, wx, B, S, fs, nl, dev)
+    if stack or (nl == 1 and _one_launch(K.gfront_persist_ok, T, wx, B, S, fs, dev)):
         pre = torch.empty(T, B, (3 if gru else 4) * S, device=dev)
         _front_pre(zc, wz, b_ih, b_hh, pre, gru)
         x = _frames_buffer(front, B, T * fs, dev)
         s = torch.empty(B, T, device=dev)
         first = torch.empty(B, dtype=torch.int32, device=dev)
         t_run = torch.empty(1, dtype=torch.int32, device=dev)
-        K.gfront_gen_persist(pre, wx, w_hh, pw, pb, sw.view(-1), sb, u.contiguous(), x, s, first, t_run,
-                             bhn=b_hh[2 * S:].contiguous() if gru else None)
+        if stack:
+            # a stacked front: ONE ag_gfront_stack_fwd launch (gen = 1); the top layer's h feeds the projection and the stop head
+            lw = [[p_.w for p_ in prep[4 * l:4 * l + 4]] for l in range(nl)]
+            K.gfront_stack_gen_persist(pre, wx, [lw[l][0] for l in range(1, nl)], [lw[l][1] for l in range(nl)],
+                                       [lw[l][2] + lw[l][3] for l in range(1, nl)], pw, pb, sw.view(-1), sb, u.contiguous(),
+                                       x, s, first, t_run)
+        else:
+            K.gfront_gen_persist(pre, wx, w_hh, pw, pb, sw.view(-1), sb, u.contiguous(), x, s, first, t_run,
+                                 bhn=b_hh[2 * S:].contiguous() if gru else None)
         return x, s, first.long(), t_run
     with torch.no_grad():
-        fn = GRUFrontFn if gru else GFrontFn
-        x, s = fn.apply(zc, front, *front.group.params())
+        x, s = (GRUFrontFn if gru else GFrontFn).apply(zc, front, *front.group.params())
     return x, s, first_stops(u.t() < torch.sigmoid(s), T), None

@@ -93,3 +93,61 @@ def test_only_times_the_one_kernel_after_a_discovery_pass(K):
     gemm()
     prof = K.Profiler.stop()
     assert sorted(prof) == [name] and prof[name]['n'] == 1, prof
+
+
+def _records(K, call):
+    """{key: launches} of one profiled call"""
+    K.Profiler.start()
+    try:
+        call()
+    finally:
+        prof = K.Profiler.stop()
+    return {k: r['n'] for k, r in prof.items()}
+
+
+def _lstm_layer(K, H, T=3, B=4, ndir=2):
+    """a forward pass of a bidirectional layer on the per-step kernels -> the closures of one more forward and of its backward"""
+    gen = torch.Generator().manual_seed(14)
+    mk = lambda *shp: [(torch.randn(*shp, generator=gen) * 0.3).cuda() for _ in range(ndir)]      # noqa: E731
+    pre0, whh = mk(T, B, 4 * H), mk(4 * H, H)
+    c_all = [torch.zeros(T + 1, B, H).cuda() for _ in range(ndir)]
+    hbuf = [torch.empty(2, B, H).cuda() for _ in range(ndir)]
+    y, dy = torch.empty(T, B, ndir * H).cuda(), torch.randn(T, B, ndir * H, generator=gen).cuda()
+    gates = [p.clone() for p in pre0]
+    dgates = [torch.empty(T, B, 4 * H).cuda() for _ in range(ndir)]
+    dhb, dcb = ([torch.empty(2, B, H).cuda() for _ in range(ndir)] for _ in range(2))
+
+    def fwd():
+        for g, p in zip(gates, pre0):
+            g.copy_(p)
+        K.lstm_seq_fwd(gates, whh, c_all, hbuf, y, None)
+    fwd()
+    return fwd, lambda: K.lstm_seq_bwd(gates, whh, c_all, dy, dgates, dhb, dcb, None)
+
+
+def test_per_step_recurrent_launches_are_filed_per_kernel(K):
+    """with the persistent launches off a layer pass is T launches: the keys and counts lstm_seq_fwd / lstm_seq_bwd and the
+    _work_seq_* models give at T = 3 - the fused step kernels at H % 16 == 0, cell backward + skinny product otherwise"""
+    old = K.PERSIST[0]
+    K.PERSIST[0] = False
+    try:
+        with K.precision('f32'):
+            fwd, bwd = _lstm_layer(K, 16)
+            assert _records(K, fwd) == {'lstm_step_fwd_kernel': 3}
+            assert _records(K, bwd) == {'lstm_step_bwd_kernel': 3}
+            fwd, bwd = _lstm_layer(K, 8)
+            assert _records(K, bwd) == {'lstm_cell_bwd2_kernel': 3, 'skinny_gemm_kernel': 2}
+        torch.cuda.synchronize()
+    finally:
+        K.PERSIST[0] = old
+
+
+def test_a_wrapper_without_a_model_is_filed_under_its_name_and_a_named_one_under_the_kernels(K):
+    x = torch.randn(4).cuda()
+    y = torch.empty(4).cuda()
+    assert _records(K, lambda: K.act_fwd(x, y, K.ACT_TANH)) == {'act_fwd': 1}
+    v = torch.randn(8).cuda()
+    last = []
+    got = _records(K, lambda: (K.vec_stats(v), last.append(K.lib.ag_last_kernel().decode())))
+    assert got == {last[0]: 1} and last[0] != 'vec_stats', (got, last)
+    torch.cuda.synchronize()
