@@ -1,12 +1,25 @@
-"""-m gpu: seeded random shapes through the conv engine and the weight-gradient kernel, fp32 and bf16 mode, against torch
-convolutions in float64 (bf16 mode: on operands rounded to bf16, which the kernels' contract defines).  The fixed layer
-tables in test_gpu_kernels.py / test_bf16.py pin the C2 shapes; this one walks the dispatch space around them - chunk
-counts of the register-pipelined staging, tiles at the signal edges, strides that are not powers of two, lengths that are
-not multiples of 4 (generic staging / element-wise epilogue), strided views, every epilogue option.
-Tolerance: 2e-4 of the largest reference value (fp32 summation order only)."""
+"""-m gpu: the convolution path walked through its dispatch space against float64 - the conv engine (six tile
+configurations, both tail pairings, the ten tap specialisations, generic / register-pipelined / solo / solo + DMA staging,
+the bf16 kernel with NW 8 and 16 and its fall-backs, aligned and unaligned scatter layouts, the single-channel streaming
+kernels and each reason they are declined, every epilogue option alone and combined), the weight gradient (three MFMA
+tiles in fp32 and bf16, each refusal of the bf16 kernel, time chunks and slice counts, halos, accumulation into a non-zero
+dw, the single-channel kernels, short workspaces) and the companions of a layer's backward (channel_sum, leaky_bwd,
+conv_o1_*), in fp32 and bf16 mode.
+
+Two passes per case (tests/conv_cases.py): integer operands, where every output must equal the float64 reference bit for
+bit, and randn operands under the bound rule of DESIGN.md section 2 (16 x the fp32 CPU model's own error, never above 1e-4
+of the output scale).  Every output sits in a sentinel-filled frame that must come back untouched; two-stage reductions run
+twice for identical bits.  The kernel name the library reports is asserted equal to the restated dispatch for every case,
+and each test ends in coverage assertions on those names and on the plan classes.  The 40 seeded shapes of the earlier
+version of this file (forward, backward-data, backward-weight) are part of the lists.  tests/test_conv_fuzz_host.py shows on
+the CPU model that the checker rejects subtly wrong kernels.  Each test prints the largest real-pass error / floor per
+kernel form (pytest -s)."""
+import ctypes as C
+
 import pytest
 import torch
-import torch.nn.functional as F
+
+from tests import conv_cases as CC
 
 pytestmark = pytest.mark.gpu
 
@@ -18,94 +31,150 @@ def K():
     return K_
 
 
-def _rnd(t):
-    return t.to(torch.bfloat16).to(torch.float32)
+def test_constants_restated_in_the_case_module_match_the_library(K):
+    """tests/conv_cases.py states the activation codes, the slope and the wrappers' small workspace itself (it is imported
+    by the host test, which has no library): a drift would otherwise show only indirectly, and for the kernels that report no
+    name not at all"""
+    assert (CC.ACT_NONE, CC.ACT_LEAKY, CC.ACT_TANH, CC.ACT_LEAKY_GATE) == (K.ACT_NONE, K.ACT_LEAKY, K.ACT_TANH, K.ACT_LEAKY_GATE)
+    assert CC.LEAKY_SLOPE == K.LEAKY_SLOPE and CC.REAL['slope'] == K.LEAKY_SLOPE
+    assert CC.SMALL_WS == K._SMALL_WS
 
 
-def _cases(n, seed):
-    gen = torch.Generator().manual_seed(seed)
+def _last(K):
+    return lambda: K.lib.ag_last_kernel().decode()
 
-    def ri(lo, hi):
-        return int(torch.randint(lo, hi + 1, (1,), generator=gen))
-    out = []
-    while len(out) < n:
-        kind = 'conv' if ri(0, 1) == 0 else 'convT'
-        s = [1, 2, 2, 3, 4, 4, 8][ri(0, 6)]
-        k = ri(max(1, s - 1), 2 * s + 3)
-        p = ri(0, k - 1) if kind == 'conv' else ri(0, min(k - 1, 5))
-        cin = [1, 3, 16, 17, 24, 40, 64, 96, 130][ri(0, 8)]
-        cout = [1, 5, 16, 32, 33, 70, 128, 200][ri(0, 7)]
-        lin = [7, 64, 100, 256, 333, 512, 1000, 1024][ri(0, 7)]
-        B = ri(1, 3)
-        lout = (lin + 2 * p - k) // s + 1 if kind == 'conv' else (lin - 1) * s - 2 * p + k
-        if lout < 1 or (kind == 'conv' and lin + 2 * p < k):
-            continue
-        opts = dict(bias=ri(0, 1), res=ri(0, 1), lens=ri(0, 1), act=ri(0, 2), acc=ri(0, 1), view=ri(0, 1))
-        if opts['act'] == 2:
-            opts['res'] = 1          # act 2 = ACT_LEAKY_GATE: `res` is the saved activation that gates the result
-        out.append((kind, cin, cout, k, s, p, lin, B, opts))
-    return out
+
+def _report(what, prec, worst):
+    print('conv fuzz, %s, %s mode: largest real-pass error / floor per kernel form' % (what, prec))
+    for form in sorted(worst):
+        print('  %-44s %6.2f' % (form, worst[form]))
+
+
+def _form(pl):
+    return pl['kernel'] + ' ' + pl['form']
 
 
 @pytest.mark.parametrize('prec', ['f32', 'bf16'])
-def test_conv_engine_and_wgrad_random_shapes(K, prec):
-    from audiogan_amd import ops
-    old = K.set_precision(prec)
-    try:
-        for ci, (kind, cin, cout, k, s, p, lin, B, o) in enumerate(_cases(40, 77)):
-            tag = (ci, kind, cin, cout, k, s, p, lin, B, o)
-            gen = torch.Generator().manual_seed(1000 + ci)
-            w = torch.randn((cout, cin, k) if kind == 'conv' else (cin, cout, k), generator=gen) / (cin * k) ** 0.5
-            x = torch.randn(B, cin, lin, generator=gen)
-            spec = ops.ConvSpec(kind, cin, cout, k, s, p)
-            lout = spec.out_len(lin)
-            dy = torch.randn(B, cout, lout, generator=gen)
-            bias = torch.randn(cout, generator=gen) if o['bias'] else None
-            res = torch.randn(B, cout, lout, generator=gen) if o['res'] else None
-            lens = torch.randint(1, lout + 1, (B,), generator=gen) if o['lens'] else None
-            y0 = torch.randn(B, cout, lout, generator=gen)
-            r = _rnd if prec == 'bf16' else (lambda t: t)
-            xr, wr = r(x).double().requires_grad_(True), r(w).double().requires_grad_(True)
-            lin_out = F.conv1d(xr, wr, None, s, p) if kind == 'conv' else F.conv_transpose1d(xr, wr, None, s, p)
-            v = lin_out
-            if bias is not None:
-                v = v + bias.double().view(1, -1, 1)
-            if res is not None and o['act'] == 2:
-                v = v * torch.where(res > 0, torch.ones_like(res), torch.full_like(res, K.LEAKY_SLOPE)).double()
-            elif res is not None:
-                v = v + res.double()
-            if o['act'] == 1:
-                v = F.leaky_relu(v, K.LEAKY_SLOPE)
-            if lens is not None:
-                v = v * (torch.arange(lout).view(1, 1, -1) < lens.view(B, 1, 1)).double()
-            ref = v + y0.double() if o['acc'] else v
-            d0, d1, _ = w.shape
-            prep = ops.Prepared(w=w.cuda(), wpa=torch.zeros(K.wpa_numel(d0, d1, k)).cuda(),
-                                wpb=torch.zeros(K.wpb_numel(d0, d1, k, s)).cuda(), pad=p)
-            K.prep_conv_weight(prep.w, prep.wpa, prep.wpb, s, p)
-            xg = x.cuda()
-            if o['view']:            # a channel slice of a wider slab with a padded row pitch: strided batch / channel strides
-                slab = torch.zeros(B, cin + 2, lin + 12).cuda()
-                slab[:, 1:cin + 1, 4:lin + 4] = xg
-                xg = slab[:, 1:cin + 1, 4:lin + 4]
-            y = y0.cuda().clone()
-            K.conv_engine(xg, prep.wpa if kind == 'conv' else prep.wpb, y, k, s, p, 0 if kind == 'conv' else 1,
-                          bias=bias.cuda() if bias is not None else None, res=res.cuda() if res is not None else None,
-                          lens=lens.cuda() if lens is not None else None, act=(K.ACT_NONE, K.ACT_LEAKY, K.ACT_LEAKY_GATE)[o['act']],
-                          accumulate=bool(o['acc']), wp_pad=p)
-            scale = max(1.0, float(ref.detach().abs().max()))
-            err = float((y.cpu().double() - ref.detach()).abs().max())
-            assert err <= 2e-4 * scale, ('forward', tag, err)
-            # backward-data and backward-weight of the plain convolution
-            dyr = r(dy).double()
-            lin_out.backward(dyr)
-            dx = torch.full((B, cin, lin), float('nan')).cuda()
-            ops.conv_bwd_data(spec, prep, dy.cuda(), dx)
-            err = float((dx.cpu().double() - xr.grad).abs().max())
-            assert err <= 2e-4 * max(1.0, float(xr.grad.abs().max())), ('backward-data', tag, err)
-            dw = torch.zeros_like(w).cuda()
-            ops.conv_wgrad(spec, xg, dy.cuda(), dw, None)
-            err = float((dw.cpu().double() - wr.grad).abs().max())
-            assert err <= 2e-4 * max(1.0, float(wr.grad.abs().max())), ('backward-weight', tag, err)
-    finally:
-        K.set_precision(old)
+def test_conv_engine_cases(K, prec):
+    seen, worst = [], {}
+    with K.precision(prec):
+        for ci, (label, c) in enumerate(CC.engine_cases()):
+            pl = CC.conv_plan(prec, c)
+            for pas in (CC.EXACT, CC.REAL):
+                inp = CC.engine_inputs(c, pas, 1000 + ci)
+                ref = CC.engine_reference(c, pas, inp, rounded=prec == 'bf16')
+                floor = CC.engine_floor(c, pas, inp, rounded=prec == 'bf16') if pas is CC.REAL else None
+                got = CC.run_engine(K, c, pas, inp, 'cuda', last_kernel=_last(K))
+                assert got['kernel'] == pl['kernel'], ('the restated dispatch and the library disagree', label, c, got['kernel'], pl['kernel'])
+                ratio = CC.check((label, c), pas, ref, got, floor=floor, form=_form(pl), output='y')
+                worst[_form(pl)] = max(worst.get(_form(pl), 0.0), ratio)
+            seen.append((label, c, got['kernel'], pl))
+    _report('engine', prec, worst)
+    CC.assert_engine_coverage(prec, seen)
+
+
+@pytest.mark.parametrize('prec', ['f32', 'bf16'])
+def test_conv_wgrad_cases(K, prec):
+    seen, worst = [], {}
+    with K.precision(prec):
+        for ci, (label, c) in enumerate(CC.wgrad_cases()):
+            pl = CC.wgrad_plan(prec, c)
+            assert K.lib.ag_conv1d_wgrad_ws_numel(c.B, c.A, c.Lsh, c.C, c.K) == pl['ws_want'], (label, c)
+            for pas in (CC.EXACT, CC.REAL):
+                inp = CC.wgrad_inputs(c, pas, 1000 + ci)
+                ref = CC.wgrad_reference(c, pas, inp, rounded=prec == 'bf16')
+                floor = CC.wgrad_floor(c, pas, inp, rounded=prec == 'bf16') if pas is CC.REAL else None
+                got = CC.run_wgrad(K, c, pas, inp, 'cuda', last_kernel=_last(K))
+                again = CC.run_wgrad(K, c, pas, inp, 'cuda', last_kernel=_last(K))      # two-stage, fixed order
+                assert got['kernel'] == pl['kernel'], ('the restated dispatch and the library disagree', label, c, got['kernel'], pl['kernel'])
+                ratio = CC.check((label, c), pas, ref, got, floor=floor, form=pl['kernel'], output='dw', again=again)
+                worst[pl['kernel']] = max(worst.get(pl['kernel'], 0.0), ratio)
+            seen.append((label, c, got['kernel'], pl))
+    _report('weight gradient', prec, worst)
+    CC.assert_wgrad_coverage(prec, seen)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def test_conv_wgrad_workspace_sizes(K):
+    """the slice count is capped by the bound workspace: the full one (16 slabs), three slabs and a bit, exactly one slab -
+    the result is right every time, exact on integers - and below one slab the documented argument error, after which the
+    next call does not find the failed call's binding"""
+    c = CC.WS_CASE
+    n_out = c.A * c.C * c.K
+    full = K.lib.ag_conv1d_wgrad_ws_numel(c.B, c.A, c.Lsh, c.C, c.K)
+    assert full == CC.wgrad_plan('f32', c)['ws_want'] and full // n_out > 3
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def raw(numel, ws):
+        def call(sh, lg, dw, K_, s, p):
+            if numel:
+                assert K.lib.ag_bind_workspace(_ptr(ws), numel) == 0
+            else:
+                K.lib.ag_bind_workspace(None, 0)
+            call.rc = K.lib.ag_conv1d_wgrad(_ptr(sh), sh.stride(0), sh.stride(1), _ptr(lg), lg.stride(0), lg.stride(1), _ptr(dw),
+                                            c.B, c.A, c.Lsh, c.C, c.Llg, K_, s, p, stream)
+            call.err = K.lib.ag_last_error()
+        return call
+    with K.precision('f32'):
+        for pas in (CC.EXACT, CC.REAL):
+            inp = CC.wgrad_inputs(c, pas, 7)
+            ref, floor = CC.wgrad_reference(c, pas, inp), CC.wgrad_floor(c, pas, inp)
+            for numel in (full, 3 * n_out + 5, n_out):
+                ws = torch.full((numel + 64,), CC.SENTINEL, device='cuda')
+                call = raw(numel, ws)
+                got = CC.run_wgrad(K, c, pas, inp, 'cuda', last_kernel=_last(K), call=call)
+                assert call.rc == 0, call.err
+                assert got['kernel'] == 'conv_wgrad_kernel<2,2,2,2>'
+                CC.check(('workspace', numel), pas, ref, got, floor=floor, form=got['kernel'], output='dw')
+                assert bool((ws[numel:] == CC.SENTINEL).all()), 'wrote past the bound workspace'
+                used = CC.wgrad_plan('f32', c, numel)['gz'] * n_out
+                assert bool((ws[used:numel] == CC.SENTINEL).all()), 'more slabs written than the plan says'
+        # below one slab, and none at all: the documented error, dw untouched
+        inp = CC.wgrad_inputs(c, CC.EXACT, 7)
+        for numel in (n_out - 1, 0):
+            ws = torch.full((n_out + 64,), CC.SENTINEL, device='cuda')
+            call = raw(numel, ws)
+            got = CC.run_wgrad(K, c, CC.EXACT, inp, 'cuda', call=call)
+            assert call.rc == -1 and b'needs a workspace of >= %d floats' % n_out in call.err, (call.rc, call.err)
+            assert torch.equal(got['out'], inp['dw0']) and got['frame_ok']
+            assert bool((ws == CC.SENTINEL).all())
+        # the binding is taken FIRST: an argument error must not leave it to the next call
+        ws = torch.full((full,), CC.SENTINEL, device='cuda')
+
+        def call2(sh, lg, dw, K_, s, p):
+            assert K.lib.ag_bind_workspace(_ptr(ws), full) == 0
+            rc = K.lib.ag_conv1d_wgrad(_ptr(sh), sh.stride(0), sh.stride(1), _ptr(lg), lg.stride(0), lg.stride(1), _ptr(dw),
+                                       0, c.A, c.Lsh, c.C, c.Llg, K_, s, p, stream)
+            assert rc == -1 and b'bad shape' in K.lib.ag_last_error()
+            rc = K.lib.ag_conv1d_wgrad(_ptr(sh), sh.stride(0), sh.stride(1), _ptr(lg), lg.stride(0), lg.stride(1), _ptr(dw),
+                                       c.B, c.A, c.Lsh, c.C, c.Llg, K_, s, p, stream)
+            assert rc == -1, 'the call after a failed one found the failed call\'s workspace'
+        got = CC.run_wgrad(K, c, CC.EXACT, inp, 'cuda', call=call2)
+        assert torch.equal(got['out'], inp['dw0']) and got['frame_ok'], 'a call that failed its argument check wrote dw'
+        assert bool((ws == CC.SENTINEL).all())
+
+
+@pytest.mark.parametrize('prec', ['f32', 'bf16'])
+def test_conv_small_kernels(K, prec):
+    seen, worst = [], {}
+    with K.precision(prec):
+        for ci, (label, c) in enumerate(CC.small_cases()):
+            pl = CC.small_plan(c)
+            rounded = prec == 'bf16' and c.op.startswith('o1')
+            for pas in (CC.EXACT, CC.REAL):
+                inp = CC.small_inputs(c, pas, 1000 + ci)
+                ref = CC.small_reference(c, pas, inp, rounded)
+                low = CC.small_reference(c, pas, inp, rounded, dtype=torch.float32)
+                got = CC.run_small(K, c, pas, inp, 'cuda')
+                again = CC.run_small(K, c, pas, inp, 'cuda') if pl['twostage'] else None
+                assert set(got) == set(ref)
+                for k in ref:
+                    ratio = CC.check((label, c, k), pas, ref[k], got[k], floor=CC.floor_of(low[k], ref[k]), form=pl['kernel'], output=k,
+                                     again=again[k] if again else None)
+                    worst[pl['kernel'] + ':' + k] = max(worst.get(pl['kernel'] + ':' + k, 0.0), ratio)
+            seen.append((label, c, pl))
+    _report('small kernels', prec, worst)
+    CC.assert_small_coverage(seen)
