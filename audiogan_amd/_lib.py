@@ -192,6 +192,10 @@ SIGNATURES = {
                                    C.c_int, vp]),
     'ag_clip_facts': (C.c_int, [vp, vp, vp, vp, vp, i64, vp]),
     'ag_clip_gather': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp, C.c_int, vp]),
+    'ag_join_max_segments': (C.c_int, []),
+    'ag_join_facts': (C.c_int, [vp, i64, C.c_int, vp, vp, C.c_int, f32, vp, vp, vp]),
+    'ag_join_clips': (C.c_int, [vp, i64, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
+                                i64, C.c_int, vp, vp]),
     'ag_frame_power_ok': (C.c_int, [C.c_int] * 2),
     'ag_frame_power_tile': (C.c_int, [C.c_int] * 2),
     'ag_frame_power': (C.c_int, [vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, i64, i64, i64, C.c_int, vp]),

@@ -24,10 +24,21 @@ WAVE_FORMAT_IEEE_FLOAT = 3
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
 
 
-def write_wav(path, samples, sr=8000):
-    """write ``samples`` (1-D, any float array or tensor) to ``path`` as a mono 32-bit float WAV at ``sr`` Hz"""
+def write_wav(path, samples, sr=8000, fmt='float32'):
+    """write ``samples`` (1-D, any float array or tensor) to ``path`` as a mono WAV at ``sr`` Hz: 32-bit floats (format tag 3)
+    by default; ``fmt='pcm16'``: 16-bit PCM (format tag 1), clip(rint(x * 32767), -32768, 32767)"""
     if hasattr(samples, 'detach'):
         samples = samples.detach().cpu().numpy()
+    if fmt == 'pcm16':
+        x = np.asarray(samples, dtype=np.float32).reshape(-1).astype(np.float64)
+        data = np.clip(np.rint(x * 32767.0), -32768, 32767).astype('<i2').tobytes()
+        fmt_chunk = struct.pack('<HHIIHH', WAVE_FORMAT_PCM, 1, int(sr), int(sr) * 2, 2, 16)
+        body = b'WAVE' + b'fmt ' + struct.pack('<I', len(fmt_chunk)) + fmt_chunk + b'data' + struct.pack('<I', len(data)) + data
+        with open(path, 'wb') as f:
+            f.write(b'RIFF' + struct.pack('<I', len(body)) + body)
+        return
+    if fmt != 'float32':
+        raise ValueError("audiogan_amd: write_wav writes 'float32' or 'pcm16', not %r" % (fmt,))
     data = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1)).astype('<f4').tobytes()
     channels, bits = 1, 32
     block = channels * bits // 8

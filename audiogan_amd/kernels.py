@@ -2290,3 +2290,90 @@ def activity_segments(power, nf, lens, ratio, floor, min_gap, min_run, pad, win,
     return seg, count, pmax
 
 
+
+
+# ------------------------------------------------------------------------------------
+# sentence synthesis (synth.Voice.say_batch): the facts of ragged rows, the rows joined into sentences - no host read
+# ------------------------------------------------------------------------------------
+JOIN_MAX_SEGMENTS = int(lib.ag_join_max_segments())       # segments one sentence of ag_join_clips may hold
+JOIN_MAX_FADE = 4096                                       # samples: the longest ramp of ag_join_clips
+_RAMPS = {}
+
+
+def join_ramp(F, device='cpu'):
+    """fp32 [F] on ``device``: ramp[i] = sin^2(pi (i + 0.5) / (2 F)), evaluated in float64 and rounded once; strictly rising,
+    ramp[i] + ramp[F - 1 - i] = 1 within 3e-8 - an overlap of exactly F samples is a constant-gain crossfade.  Cached per
+    (F, device)."""
+    F = int(F)
+    if not 0 <= F <= JOIN_MAX_FADE:
+        raise ValueError('audiogan_amd: a fade of %d samples: 0 .. %d' % (F, JOIN_MAX_FADE))
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if (F, 'cpu') not in _RAMPS:
+        r = np.sin(np.pi * (np.arange(F, dtype=np.float64) + 0.5) / (2.0 * max(F, 1))) ** 2
+        _RAMPS[(F, 'cpu')] = torch.from_numpy(r.astype(np.float32))
+    if (F, str(device)) not in _RAMPS:
+        _RAMPS[(F, str(device))] = _RAMPS[(F, 'cpu')].to(device)
+    return _RAMPS[(F, str(device))]
+
+
+def _join_rows(wave, off, n):
+    """the checks both launches share: fp32 rows of unit stride along the samples, one int32 offset and length per row
+    -> (R, L_in, row pitch)"""
+    _chk(wave, 'wave'); _chk(off, 'off', torch.int32); _chk(n, 'n', torch.int32)
+    if wave.dim() != 2 or (wave.size(1) > 1 and wave.stride(1) != 1):
+        raise ValueError('audiogan_amd: wave must be [R, L_in] with unit stride along L_in, got %r with strides %r'
+                         % (tuple(wave.shape), wave.stride()))
+    R, L_in = wave.size(0), wave.size(1)
+    if tuple(off.shape) != (R,) or tuple(n.shape) != (R,) or not off.is_contiguous() or not n.is_contiguous():
+        raise ValueError('audiogan_amd: off and n must be contiguous vectors with one entry per row of wave (%d)' % R)
+    return R, L_in, wave.stride(0) if R > 1 else max(wave.stride(0), L_in)
+
+
+# (neither launch is in the Profiler's timed set: that set is the training step's launches, which the bench's profile reports)
+def join_facts(wave, off, n, target=0.0):
+    """``wave`` fp32 [R, L_in] (unit stride along the samples, any row pitch), ``off`` / ``n`` int32 [R] on the device: row r's
+    window is wave[r, off' : off' + n'], both clamped into the row.  -> (gain fp32 [R], bad int32 [R]): bad = 1 when the
+    window holds a NaN or an infinity (gain 0 then), else gain = target / max |x| correctly rounded, 1 for a silent window
+    or when ``target`` <= 0 (ag_join_facts: one launch, one workgroup per row, no host read)."""
+    R, L_in, ld = _join_rows(wave, off, n)
+    gain = torch.empty(R, dtype=torch.float32, device=wave.device)
+    bad = torch.empty(R, dtype=torch.int32, device=wave.device)
+    check(lib.ag_join_facts(_p(wave), ld, L_in, _p(off), _p(n), R, float(target), _p(gain), _p(bad), _stream()), 'ag_join_facts')
+    return gain, bad
+
+
+def join_clips(wave, off, n, gain, seg_row, join, sent_ptr, ramp, out, out_len=None, pause_max=0):
+    """the windows of ``join_facts`` placed into sentences.  ``seg_row`` / ``join`` int32 [K], ``sent_ptr`` int32 [S + 1] on the
+    device: sentence s owns segments sent_ptr[s] .. sent_ptr[s + 1] - 1 (at most JOIN_MAX_SEGMENTS: the CALLER's duty beyond
+    K <= 1024 S), segment k is the window of row seg_row[k], join[k] >= 0 a pause of that many zero samples after it (at most
+    ``pause_max``, a host integer), join[k] < 0 an overlap of min(-join[k], n_k / 2, n_{k+1} / 2) samples.  ``ramp`` fp32 [F]
+    (``join_ramp``; F = 0: no fades) shapes the first and last min(F, n_k / 2) samples of every segment; ``gain`` fp32 [R]
+    scales its row.  ``out`` fp32 [S, O_cap], unit stride along O_cap, any row pitch and alignment: EVERY entry is written
+    (zeros in pauses and past a sentence's end); ``out_len`` int64 [S] receives each sentence's total, not cropped to O_cap.
+    The arithmetic is the header's: products and sums rounded once each (ag_join_clips: one launch).  -> (out, out_len)"""
+    R, L_in, ld = _join_rows(wave, off, n)
+    _chk(gain, 'gain'); _chk(seg_row, 'seg_row', torch.int32); _chk(join, 'join', torch.int32)
+    _chk(sent_ptr, 'sent_ptr', torch.int32); _chk(ramp, 'ramp'); _chk(out, 'out'); _chk(out_len, 'out_len', torch.int64)
+    if tuple(gain.shape) != (R,) or not gain.is_contiguous():
+        raise ValueError('audiogan_amd: gain must be a contiguous vector with one entry per row of wave (%d)' % R)
+    if seg_row.dim() != 1 or tuple(join.shape) != tuple(seg_row.shape) or not seg_row.is_contiguous() or not join.is_contiguous():
+        raise ValueError('audiogan_amd: seg_row and join must be contiguous vectors with one entry per segment')
+    if sent_ptr.dim() != 1 or sent_ptr.numel() < 1 or not sent_ptr.is_contiguous():
+        raise ValueError('audiogan_amd: sent_ptr must be a contiguous vector of S + 1 entries')
+    if ramp.dim() != 1 or not ramp.is_contiguous():
+        raise ValueError('audiogan_amd: ramp must be a contiguous vector (kernels.join_ramp)')
+    K_, S = seg_row.numel(), sent_ptr.numel() - 1
+    if out.dim() != 2 or out.size(0) != S or (out.size(1) > 1 and out.stride(1) != 1):
+        raise ValueError('audiogan_amd: out must be [%d, O_cap] with unit stride along O_cap, got %r with strides %r'
+                         % (S, tuple(out.shape), out.stride()))
+    if out_len is None:
+        out_len = torch.empty(S, dtype=torch.int64, device=out.device)
+    if tuple(out_len.shape) != (S,) or not out_len.is_contiguous():
+        raise ValueError('audiogan_amd: out_len must be a contiguous vector of %d entries' % S)
+    O_cap = out.size(1)
+    ldo = out.stride(0) if S > 1 else max(out.stride(0), O_cap)
+    check(lib.ag_join_clips(_p(wave), ld, L_in, _p(off), _p(n), _p(gain), R, _p(seg_row), _p(join), _p(sent_ptr), K_, S,
+                            int(pause_max), _p(ramp), ramp.numel(), _p(out), ldo, O_cap, _p(out_len), _stream()), 'ag_join_clips')
+    return out, out_len

@@ -879,6 +879,53 @@ int ag_clip_gather(const float* bank, const long long* start, const int32_t* n, 
                    int B, float* out, long long ld_out, int L_out, long long* len_out, int frame, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * ag_join_facts, ag_join_clips (csrc/join.hip): generated words put next to each other on the device (synth.Voice.say_batch).
+ * The rows are ragged clips whose lengths are on the device; both launches read them there, so a sentence is joined with no
+ * host read.  The reference has no inference path (audiogan.py trains and logs).  fp32 whatever ag_set_precision says; no
+ * atomics, no workspace, one launch each.
+ *   The window of row r < R: wave[r * ld + off' .. + n'), off' = clamp(off[r], 0, L_in), n' = clamp(n[r], 0, L_in - off')
+ *   (off, n int32 on the device; off is arbitrary, so samples are loaded 4 bytes at a time).
+ *   ag_join_facts   per row: the peak = the largest |x| bit pattern of the window (as ag_clip_facts forms it);
+ *                     bad_out[r] (int32) = 1 when that pattern is >= +inf's - the window holds a NaN or an infinity - and
+ *                     gain_out[r] = 0 then; else gain_out[r] = peak > 0 ? target / peak (correctly rounded) : 1.
+ *                     target <= 0: every gain is 1 (bad is still formed).  n' = 0: peak 0.  Order-free: exact.
+ *                   One workgroup per row.                                                              "join_facts_kernel"
+ *   ag_join_clips   sentence s < S owns segments k = sent_ptr[s] .. sent_ptr[s + 1] - 1 (int32 [S + 1], ascending, within
+ *                   0 .. K; at most ag_join_max_segments() = 1024 of them); segment k is the window of row seg_row[k] (int32
+ *                   [K]; a row may serve any number of segments).  THE PLAN of a sentence, in integers, n_k its windows' n':
+ *                     f_k = min(F, n_k / 2)                                   the fade length of segment k
+ *                     join[k] >= 0: a pause of min(join[k], pause_max) zero samples between k and k + 1
+ *                     join[k] <  0: an overlap ov_k = min(-join[k], n_k / 2, n_{k+1} / 2)          (integer divisions)
+ *                     st_0 = 0,  st_{k+1} = st_k + n_k + pause  or  st_k + n_k - ov_k;  the sentence's last join is ignored
+ *                     total = st_last + n_last (0 for an empty sentence);  out_len[s] (int64) = total, NOT cropped to O_cap.
+ *                   With these clamps at most two segments cover a sample: k* = the last k with st_k <= t, and k* - 1.
+ *                   Sample i of segment k, j = n_k - 1 - i, weighs w = ramp[(i F) / f_k] if i < f_k, ramp[(j F) / f_k] if
+ *                   j < f_k, else 1 (the two regions cannot meet), with the coefficient c = fmul(gain[row], w).  For t < O_cap:
+ *                     two covering segments a < b:  out[s * ld_out + t] = fadd(fmul(x_a, c_a), fmul(x_b, c_b))
+ *                     one:                          fmul(x, c)
+ *                     none (a pause, t >= total):   0
+ *                   each operation rounded once to fp32 - never a contracted fma.  EVERY t < O_cap of every sentence is
+ *                   written.  ramp: fp32 [F] on the device (kernels.join_ramp: sin^2(pi (i + 0.5) / (2 F)), float64 rounded
+ *                   once), not read when F = 0.  Grid (ceil(O_cap / 1024), S); every workgroup forms its sentence's plan in
+ *                   LDS (one exclusive scan of 1024 advances), then each thread takes four consecutive samples: one binary
+ *                   search, one 16-byte store when out is 16-byte aligned and ld_out % 4 == 0, four 4-byte stores
+ *                   otherwise - the same bits.                          "join_clips_kernel<1>" (16-byte) / "<0>" (scalar)
+ *                   What the tables hold cannot send a load outside wave: a seg_row outside 0 .. R - 1 is an empty segment,
+ *                   sent_ptr is clamped to 0 .. K, segments past a sentence's 1024th are dropped.
+ *   Refused from host code before any HIP call (AG_ERR_ARG): a negative R, L_in, K, O_cap or pause_max; S outside 0 .. 65535;
+ *   F outside 0 .. 4096; K > 1024 S (some sentence holds more than ag_join_max_segments(); a sentence's own count is on the
+ *   device: the CALLER's duty, synth.Voice checks it on the host); min(K, 1024) (L_in + pause_max) > 2^31 - 1 (a sentence
+ *   could pass the int32 plan); ld < L_in; ld_out < O_cap; a null pointer with work to do; a NaN target.  R = 0 (facts) or
+ *   S = 0 (clips): AG_OK with no launch.
+ * ------------------------------------------------------------------------- */
+int ag_join_max_segments(void);
+int ag_join_facts(const float* wave, long long ld, int L_in, const int32_t* off, const int32_t* n, int R, float target,
+                  float* gain_out, int32_t* bad_out, void* stream);
+int ag_join_clips(const float* wave, long long ld, int L_in, const int32_t* off, const int32_t* n, const float* gain, int R,
+                  const int32_t* seg_row, const int32_t* join, const int32_t* sent_ptr, int K, int S, int pause_max,
+                  const float* ramp, int F, float* out, long long ld_out, int O_cap, long long* out_len, void* stream);
+
+/* ---------------------------------------------------------------------------
  * ag_frame_power, ag_activity_segments (csrc/activity.hip): short-time energy activity detection on the resampled rows
  * (audio.activity, ingest.build_store(trim / split)).  They stand where the reference's preprocessing cuts words by a forced
  * alignment (preprocess-fisher.py:145-146) or keeps windows by an amplitude threshold (preprocess.py:25-27).  fp32 whatever
