@@ -162,22 +162,47 @@ class Frame(object):
 
 
 class FlatFrame(object):
-    """a contiguous tensor of `shape` between guard floats"""
+    """a contiguous tensor of `shape` between guard floats (`dtype`: fp32, or bf16 / an integer type for the outputs of the
+    pointwise fuzz that are stored so)"""
 
-    def __init__(self, shape, device, fill):
+    def __init__(self, shape, device, fill, dtype=torch.float32):
         n = 1
         for s in shape:
             n *= s
-        self.n = n
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.float32, device=device)
-        self.win = self.buf[GUARD:GUARD + n].view(*shape)
+        self.n, self.lo = n, GUARD
+        self.bits = {4: torch.int32, 2: torch.int16, 8: torch.int64}[torch.empty(0, dtype=dtype).element_size()]
+        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=device)
+        self.win = self.buf[self.lo:self.lo + n].view(*shape)
         self.win.copy_(fill)
         self.before = self.buf.cpu().clone()
 
     def untouched(self):
         after = self.buf.cpu()
-        return torch.equal(after[:GUARD].view(torch.int32), self.before[:GUARD].view(torch.int32)) and \
-            torch.equal(after[GUARD + self.n:].view(torch.int32), self.before[GUARD + self.n:].view(torch.int32))
+        return torch.equal(after[:self.lo].view(self.bits), self.before[:self.lo].view(self.bits)) and \
+            torch.equal(after[self.lo + self.n:].view(self.bits), self.before[self.lo + self.n:].view(self.bits))
+
+    def window(self):
+        return self.win.cpu().clone()
+
+
+class StridedFrame(object):
+    """a window of `shape` and any `strides` (in floats, from `off` floats behind the front guard) inside a sentinel-filled
+    buffer: a transposed view, a column of a wider tensor, a view with no unit stride"""
+
+    def __init__(self, shape, strides, off, device, fill, sentinel=SENTINEL):
+        span = 1 + sum((n - 1) * st for n, st in zip(shape, strides))
+        self.buf = torch.full((off + span + 2 * GUARD,), sentinel, dtype=torch.float32, device=device)
+        self.geo = (tuple(shape), tuple(strides), GUARD + off)
+        self.win = self.buf.as_strided(*self.geo)
+        if fill is not None:
+            self.win.copy_(fill)
+        self.before = self.buf.cpu().clone()
+
+    def untouched(self):
+        after, before = self.buf.cpu().clone(), self.before.clone()
+        for t in (after, before):
+            t.as_strided(*self.geo).zero_()
+        return torch.equal(after.view(torch.int32), before.view(torch.int32))
 
     def window(self):
         return self.win.cpu().clone()

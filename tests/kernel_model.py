@@ -191,10 +191,11 @@ def gemm(A, B, Cm, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, res=None,
 
 
 def col_sum(X, out, accumulate=True, defer=True):
+    s = X.float().sum(0)                 # (X may be stored as bf16; the sum is taken in fp32)
     if accumulate:
-        out.add_(X.sum(0))
+        out.add_(s)
     else:
-        out.copy_(X.sum(0))
+        out.copy_(s)
 
 
 def lstm_cell_fwd(gates, c_prev, c_out, h_out=None, y_out=None, h_prev=None, valid=None, t=0):
@@ -371,9 +372,9 @@ def gfront_persist_ok(B, S, fs, dev):
 def bct_to_tbc(x, out=None, out_dtype=None):
     r = x.permute(2, 0, 1).contiguous()
     if out is not None:
-        out.copy_(r)
+        out.copy_(r)                     # (a bf16 `out`: torch narrows to nearest even, like the kernel)
         return out
-    return r
+    return r.to(out_dtype) if out_dtype is not None else r
 
 
 def tbc_to_bct(x, out=None, out_dtype=None):
@@ -381,7 +382,14 @@ def tbc_to_bct(x, out=None, out_dtype=None):
     if out is not None:
         out.copy_(r)
         return out
-    return r
+    return r.to(out_dtype) if out_dtype is not None else r
+
+
+def to_bf16(src, out=None):
+    if out is None:
+        return src.to(torch.bfloat16)
+    out.copy_(src.reshape(out.shape))
+    return out
 
 
 class deferred_reduces(object):
@@ -419,7 +427,7 @@ def rowdot_ok(x, w):
 
 
 def rowdot_fwd(x, w, bias, y):
-    r = x @ w.reshape(-1)
+    r = x.float() @ w.reshape(-1)        # (x may be stored as bf16)
     if bias is not None:
         r = r + bias.reshape(-1)[0]
     y.copy_(r.view(y.shape))
@@ -427,6 +435,7 @@ def rowdot_fwd(x, w, bias, y):
 
 def rowdot_bwd(dy, x, w, dx=None, dw=None, db=None, gate=False, slope=LEAKY_SLOPE, accumulate=True):
     g = dy.reshape(-1, 1)
+    x = x.float()                        # (x and dx may be stored as bf16: dx.copy_ narrows to nearest even)
     if dx is not None:
         r = g * w.reshape(1, -1)
         if gate:
@@ -607,19 +616,23 @@ def time_moments_fwd(h, lens, m, s, f):
 
 
 def time_moments_bwd(h, lens, gm, gs, gf, dh):
+    """autograd of the forward definition; in a row whose central moments are exactly zero autograd gives NaN (sqrt'(0)) and
+    the kernel documents that it drops the s / f terms there: such a row gets the gm term alone.  dh may be a pitched view"""
     with torch.enable_grad():       # called from inside an autograd backward
         hh = h.detach().clone().requires_grad_(True)
         B, C, L = hh.shape
-        mask = (torch.arange(L).view(1, L) < lens.view(B, 1)).float()
-        lf = lens.view(B, 1).float()
+        mask = (torch.arange(L).view(1, L) < lens.view(B, 1)).to(hh.dtype)
+        lf = lens.view(B, 1).to(hh.dtype)
         mm = hh.sum(2) / lf
         cen = hh - mm.unsqueeze(2) * mask.unsqueeze(1)
-        z = torch.zeros(B, C)
+        z = torch.zeros(B, C, dtype=hh.dtype)
+        s2 = (cen ** 2).sum(2)
         tot = (mm * (gm if gm is not None else z)).sum() \
-            + (((cen ** 2).sum(2) ** 0.5 / lf) * (gs if gs is not None else z)).sum() \
+            + ((s2 ** 0.5 / lf) * (gs if gs is not None else z)).sum() \
             + (((cen ** 4).sum(2) ** 0.25 / lf) * (gf if gf is not None else z)).sum()
         g, = torch.autograd.grad(tot, hh)
-    dh.copy_(g)
+    flat = (s2.detach() == 0).unsqueeze(2)
+    dh.copy_(torch.where(flat, ((gm if gm is not None else z) / lf).unsqueeze(2).expand(B, C, L), g))
 
 
 ALL = [n for n, v in list(globals().items()) if callable(v) and not n.startswith('_')
