@@ -187,6 +187,9 @@ SIGNATURES = {
     'ag_melcep_frames': (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     'ag_dtw_cost': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     'ag_dtw_pairs': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+    'ag_dtw_align_ws': (i64, [C.c_int, C.c_int]),
+    'ag_dtw_align': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]),
+    'ag_dtw_align_forward': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]),
     'ag_resample_ok': (C.c_int, [C.c_int] * 5),
     'ag_resample_poly': (C.c_int, [vp, C.c_int, C.c_int, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, vp, i64, i64, i64,
                                    C.c_int, vp]),

@@ -2130,6 +2130,44 @@ def dtw_pairs(cep_a, nf_a, cep_b, nf_b, ia=None, ib=None, out=None):
     return out
 
 
+def dtw_align_ws(Fa, Fb):
+    """bytes of decision workspace ``dtw_align`` needs PER PAIR at these capacities (two bits per cell; 0: outside 1..1024)"""
+    return int(lib.ag_dtw_align_ws(int(Fa), int(Fb)))
+
+
+# Not under @_timed: tests/test_launch_layer.py pins the timed set, and this launch belongs to data preparation (ingest
+# --utterances), which no Profiler run of training or evaluation covers.  tools/prof_dtwalign.py times it with device
+# events; the library reports it to ag_last_kernel as "dtw_align_kernel" like every other launch.
+def dtw_align(cep_a, nf_a, cep_b, nf_b, total=None, lo=None, hi=None, workspace=None):
+    """``dtw_cost`` with its path.  cep_a [B, Fa, 16] (the utterance: rows), cep_b [B, Fb, 16] (the reference: columns), nf_a /
+    nf_b int32 [B] or None -> (total [B] fp32, lo [B, Fb] int32, hi [B, Fb] int32): ``total`` has the bits of ``dtw_cost``;
+    lo[b, j] / hi[b, j] are the first / last row of a that the optimal path matches to column j, for j < nf_b[b] - columns at
+    or past the count are not written.  Ties go to the diagonal, then to (i-1, j), then to (i, j-1).  ``workspace``: a
+    device tensor of at least B * dtw_align_ws(Fa, Fb) bytes (default: allocated here) that receives two bits per cell
+    (ag_dtw_align: one launch, one workgroup per pair)."""
+    assert cep_a.dim() == 3 and cep_b.dim() == 3, (tuple(cep_a.shape), tuple(cep_b.shape))
+    B, Fa, Fb = cep_a.size(0), cep_a.size(1), cep_b.size(1)
+    dev = cep_a.device
+    if total is None:
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+    if lo is None:
+        lo = torch.empty(B, Fb, dtype=torch.int32, device=dev)
+    if hi is None:
+        hi = torch.empty(B, Fb, dtype=torch.int32, device=dev)
+    need = B * dtw_align_ws(Fa, Fb)
+    if workspace is None:
+        workspace = torch.empty(max(need, 4) // 4, dtype=torch.int32, device=dev)
+    _check_table([(cep_a, 'cep_a', (B, Fa, CEP_WIDTH)), (cep_b, 'cep_b', (B, Fb, CEP_WIDTH)),
+                  (nf_a, 'nf_a', (B,), torch.int32), (nf_b, 'nf_b', (B,), torch.int32), (total, 'total', (B,)),
+                  (lo, 'lo', (B, Fb), torch.int32), (hi, 'hi', (B, Fb), torch.int32)])
+    if not workspace.is_cuda:
+        raise RuntimeError('audiogan_amd: workspace must be a CUDA (HIP) tensor; there is no CPU path')
+    assert workspace.is_contiguous() and workspace.data_ptr() % 4 == 0, 'workspace'
+    check(lib.ag_dtw_align(_p(cep_a), _p(nf_a), _p(cep_b), _p(nf_b), _p(total), _p(lo), _p(hi), _p(workspace),
+                           workspace.numel() * workspace.element_size(), B, Fa, Fb, _stream()), 'ag_dtw_align')
+    return total, lo, hi
+
+
 # ------------------------------------------------------------------------------------
 # ingestion (audio.resample, ingest.build_store): polyphase resampling of ragged rows of PCM frames
 # ------------------------------------------------------------------------------------

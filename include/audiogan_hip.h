@@ -821,6 +821,39 @@ int ag_dtw_pairs(const float* cep_a, const int32_t* nf_a, int Na, int Fa, const 
                  int Fb, const int32_t* ia, const int32_t* ib, float* out, int P, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * ag_dtw_align (csrc/dtwalign.hip): the recursion of ag_dtw_cost WITH ITS PATH, for cutting a transcribed utterance into
+ * words against a reference sequence of word templates (audiogan_amd/align.py, ingest --utterances).
+ *   cep_a [B, Fa, 16] (the utterance: rows), cep_b [B, Fb, 16] (the reference: columns), nf_a, nf_b exactly as ag_dtw_cost
+ *   takes them: counts clamped to [1, capacity] (NULL: the capacity), columns 1..12 only, rows at or past the counts never
+ *   read, Fa, Fb <= 1024, one workgroup per pair and one thread per row of a.
+ *   total[b]   = D(n-1, m-1) with THE BITS ag_dtw_cost returns for the same pair (the same fmaf chain, sqrtf, fminf order
+ *                and d + d on the diagonal).
+ *   The path   from (n-1, m-1) back to (0, 0); at every cell it goes to the predecessor whose candidate value
+ *                D(i-1, j-1) + 2 d,  D(i-1, j) + d,  D(i, j-1) + d
+ *              equals the minimum in fp32, and among several that do to THE FIRST IN THAT ORDER: the diagonal, then
+ *              (i-1, j), then (i, j-1).  On row 0 it goes left, in column 0 up.
+ *   lo[b, j], hi[b, j]  (int32 [B, Fb]) = the first and the last row of a on the path in column j, for j < m.  lo[0] = 0,
+ *              hi[m-1] = n-1, lo[j] <= hi[j], lo[j+1] is hi[j] or hi[j] + 1.  Columns j >= m are never written.
+ *   ws, ws_bytes  the decisions, two bits per cell: ag_dtw_align_ws(Fa, Fb) = Fa * ceil(Fb / 16) * 4 bytes PER PAIR (at most
+ *              256 KB; 0 for capacities outside 1..1024), B of them, 4-byte aligned, supplied by the caller - the launcher
+ *              allocates nothing and there is no bound slot.  Each thread packs 16 consecutive columns of its row into one
+ *              word and stores it when it is full or the row ends; the walk back (thread 0, after the forward loop's last
+ *              barrier and one more) reads them, at most n + m - 2 moves, and never follows a code out of the matrix.
+ *              What the workspace holds afterwards is not part of the contract.
+ *   No atomics, no spin, no dependency between workgroups; trip counts are uniform across the workgroup and at most 2047:
+ *   two runs give the same bits.                                                                  "dtw_align_kernel"
+ *   Refused from host code before any HIP call (AG_ERR_ARG): null cep_a, cep_b, total, lo, hi or ws; B <= 0; Fa or Fb outside
+ *   1..1024; ws_bytes < B * ag_dtw_align_ws(Fa, Fb).
+ *   ag_dtw_align_forward: the same launch without the walk back (lo, hi not written) - for tools/prof_dtwalign.py, which
+ *   times it to split the cost; nothing in the package calls it.
+ * ------------------------------------------------------------------------- */
+int64_t ag_dtw_align_ws(int Fa, int Fb);
+int ag_dtw_align(const float* cep_a, const int32_t* nf_a, const float* cep_b, const int32_t* nf_b, float* total, int32_t* lo,
+                 int32_t* hi, void* ws, int64_t ws_bytes, int B, int Fa, int Fb, void* stream);
+int ag_dtw_align_forward(const float* cep_a, const int32_t* nf_a, const float* cep_b, const int32_t* nf_b, float* total,
+                         int32_t* lo, int32_t* hi, void* ws, int64_t ws_bytes, int B, int Fa, int Fb, void* stream);
+
+/* ---------------------------------------------------------------------------
  * ag_resample_poly (csrc/resample.hip): polyphase windowed-sinc resampling of ragged rows of PCM frames to the models'
  * rate (audio.resample, ingest.build_store).  Replaces librosa.load(wav, sr=8000) of the reference's preprocessing
  * (preprocess.py:24, preprocess-fisher.py:232).  fp32 whatever ag_set_precision says; no atomics, no workspace, one launch.
