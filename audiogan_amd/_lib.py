@@ -199,6 +199,9 @@ SIGNATURES = {
     'ag_join_facts': (C.c_int, [vp, i64, C.c_int, vp, vp, C.c_int, f32, vp, vp, vp]),
     'ag_join_clips': (C.c_int, [vp, i64, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
                                 i64, C.c_int, vp, vp]),
+    'ag_sheet_tile_columns': (C.c_int, []),
+    'ag_sheet_render': (C.c_int, [vp, i64, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_uint, C.c_uint, C.c_uint, C.c_int,
+                                  C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     'ag_frame_power_ok': (C.c_int, [C.c_int] * 2),
     'ag_frame_power_tile': (C.c_int, [C.c_int] * 2),
     'ag_frame_power': (C.c_int, [vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, i64, i64, i64, C.c_int, vp]),

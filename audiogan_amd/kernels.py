@@ -2415,3 +2415,41 @@ def join_clips(wave, off, n, gain, seg_row, join, sent_ptr, ramp, out, out_len=N
     check(lib.ag_join_clips(_p(wave), ld, L_in, _p(off), _p(n), _p(gain), R, _p(seg_row), _p(join), _p(sent_ptr), K_, S,
                             int(pause_max), _p(ramp), ramp.numel(), _p(out), ldo, O_cap, _p(out_len), _stream()), 'ag_join_clips')
     return out, out_len
+
+
+# ------------------------------------------------------------------------------------
+# sample sheets (sheet.render, sheet.SheetWriter): a minibatch of ragged clips drawn as one image - no host read
+# ------------------------------------------------------------------------------------
+SHEET_TILE_COLUMNS = int(lib.ag_sheet_tile_columns())     # pixel columns one workgroup of ag_sheet_render takes
+SHEET_HOP = 128                                            # samples per pixel column
+
+
+def _rgb_word(c, name):
+    r, g, b = (int(v) for v in c)
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError('audiogan_amd: the colour %s = %r: three values 0 .. 255' % (name, tuple(c)))
+    return r | (g << 8) | (b << 16)
+
+
+# (not in the Profiler's timed set: that set is the training step's launches, which the bench's profile reports)
+def sheet_render(wave, lens, power, nframes, thresholds, cmap, img, cols, Hw, gutter, bg=(32, 32, 32), paper=(255, 255, 255),
+                 ink=(0, 0, 0)):
+    """``wave`` fp32 [B, L] (unit stride along the samples, any row pitch), ``lens`` int64 [B] on the device or None (L),
+    ``power`` fp32 [B, F, 129] and ``nframes`` int32 [B] as ``melcep_frames`` leaves them, ``thresholds`` fp32 [256]
+    (``sheet.thresholds``), ``cmap`` uint8 [256, 3], ``img`` uint8 [H, W, 3] of exactly ``sheet.sheet_geometry``'s size, at any
+    byte alignment: tile b at grid cell (b div cols, b mod cols), ``Hw`` rows of waveform envelope over 129 rows of spectrogram
+    (bin 0 at the bottom), one pixel column per 128 samples, ``gutter`` pixels of ``bg`` around every tile.  The rules of both
+    halves are the header's, exact: EVERY pixel of ``img`` is written, nothing is read to the host (ag_sheet_render: one
+    launch).  -> img"""
+    if wave.dim() != 2 or power.dim() != 3 or img.dim() != 3:
+        raise ValueError('audiogan_amd: wave must be [B, L], power [B, F, 129] and img [H, W, 3], got %r, %r and %r'
+                         % (tuple(wave.shape), tuple(power.shape), tuple(img.shape)))
+    (B, L), F, (H, W) = wave.shape, power.shape[1], img.shape[:2]
+    ld = _check_table([(wave, 'wave', (B, L), _PITCHED), (lens, 'lens', (B,), torch.int64),
+                       (power, 'power', (B, F, LTAS_BINS)), (nframes, 'nframes', (B,), torch.int32),
+                       (thresholds, 'thresholds', (256,)), (cmap, 'cmap', (256, 3), torch.uint8),
+                       (img, 'img', (H, W, 3), torch.uint8)])
+    check(lib.ag_sheet_render(_p(wave), ld['wave'], _p(lens), L, _p(power), _p(nframes), F, B, _p(thresholds), _p(cmap),
+                              _rgb_word(bg, 'bg'), _rgb_word(paper, 'paper'), _rgb_word(ink, 'ink'), int(cols), int(Hw),
+                              int(gutter), _p(img), H, W, _stream()), 'ag_sheet_render')
+    return img

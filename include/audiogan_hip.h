@@ -1013,6 +1013,51 @@ int ag_activity_segments(const float* power, long long power_pitch, const int32_
                          float floor_, int min_gap, int min_run, int pad, int win, int hop, long long* seg, int K,
                          int32_t* count, float* pmax, int B, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ag_sheet_render (csrc/sheet.hip): a minibatch of ragged clips drawn as ONE contact sheet (audiogan_amd/sheet.py: render,
+ * SheetWriter) - per clip a waveform envelope over a spectrogram.  It stands where the reference plots every sample's waveform
+ * on the host (audiogan.py:639-653, :674, :930).  The clips' lengths stay on the device and nothing is read back.  fp32
+ * whatever ag_set_precision says; no atomics, no workspace, one launch; two runs give the same bytes.
+ *   wave [B, L] fp32, rows ld floats apart; n_b = clamp(lens[b], 0, L) (int64 on the device; NULL: L).  wave[b, t] is never
+ *   read for t >= n_b.  power [B, F, 129] fp32 contiguous and nframes [B] int32 as ag_melcep_frames leaves them;
+ *   nf_b = clamp(nframes[b], 0, min(F, Wt)); power[b, j, :] is never read for j >= nf_b.  thresholds fp32 [256], ascending
+ *   (sheet.thresholds); cmap uint8 [256, 3] (R, G, B).  bg, paper, ink: colours as 0x00BBGGRR.
+ *   THE GRID  Wt = ceil(L / 128) pixel columns per tile - one per hop of 128 samples - and Ht = Hw + 129 rows; tile b sits at
+ *     grid cell (b div cols, b mod cols), its top left pixel at
+ *       y0 = gutter + (b div cols) (Ht + gutter),   x0 = gutter + (b mod cols) (Wt + gutter)
+ *     and the image img, uint8 [H, W, 3] contiguous at ANY byte alignment, must be exactly
+ *       H = gutter + rows (Ht + gutter),   W = gutter + cols (Wt + gutter),   rows cols >= B.
+ *     Every pixel outside a tile - gutters, grid cells b >= B - is bg.
+ *   THE ENVELOPE, rows 0 .. Hw - 1 of a tile.  peak_b = max |wave[b, t]| over t < n_b, from 0, a NaN dropped (fmaxf: the order
+ *     does not matter).  Column j < ceil(n_b / 128) covers the samples t = 128 j .. 128 j + 127 with t < n_b; vmax and vmin are
+ *     their fmaxf / fminf (both 0 if every one is a NaN).  A value lands on the row
+ *       row(v) = (int) rintf(fminf(fmaxf(fmul(fsub(1.0f, fdiv(v, peak_b)), half), 0.0f), top)),
+ *       half = 0.5f * (float)(Hw - 1),   top = (float)(Hw - 1)
+ *     each operation rounded once to fp32 (fdiv correctly rounded, as in ag_clip_gather; never a contracted fma), rintf to the
+ *     nearest even: +peak is row 0, -peak row Hw - 1.  Rows min(row(vmax), row(vmin)) .. max(..) are ink, the others paper.
+ *     peak_b = 0: the one row (Hw - 1) div 2 is ink in every such column.  Columns j >= ceil(n_b / 128) are bg.
+ *   THE SPECTROGRAM, rows Hw .. Hw + 128 of a tile; row Hw + s shows bin k = 128 - s: bin 0 is at the bottom.
+ *     Pmax_b = the fmaxf of power[b, j, k] over j < nf_b, all k, from 0 (order-free: exact).  For j < nf_b and
+ *     P = power[b, j, k] the level is the largest l with P >= fmul(thresholds[l], Pmax_b); 0 if there is none (so for a NaN
+ *     P) or if Pmax_b is 0.  The pixel is cmap[level].  No logarithm is taken: the host folds it into the table,
+ *     thresholds[l] = fp32(10^((l / 255 - 1) range_db / 10)), and the search (8 steps over the table in LDS) is exact where
+ *     a logf would differ between devices and libraries.  Columns j >= nf_b are bg.
+ *   One workgroup per (grid cell, tile of ag_sheet_tile_columns() = 32 columns); its prologue redoes the clip's two maxima,
+ *   stages the tile's frames of power in LDS as they lie in memory and reads them back across the frames at the odd pitch
+ *   129, and forms the envelope rows of its columns one wave per column.  The workgroups' rectangles - a tile's columns with
+ *   the gutter below, the gutter to the right behind a tile's last column, the sheet's top / left gutter with the first row /
+ *   column of cells - tile the image: EVERY pixel is written exactly once.  A chunk of 32 pixel rows is formed in LDS at the byte
+ *   phase its row has in memory and stored as whole dwords; single bytes only at a row segment's ragged ends.
+ *                                                                                                    "sheet_render_kernel"
+ *   Refused from host code before any HIP call (AG_ERR_ARG): a null wave, power, nframes, thresholds, cmap or img; B, F or
+ *   L <= 0; L above 2^30; ld < L; Hw outside 3 .. 4096; gutter outside 0 .. 16; cols <= 0; an H x W that is not the grid's
+ *   exactly; more than 65535 grid cells.
+ * ------------------------------------------------------------------------- */
+int ag_sheet_tile_columns(void);
+int ag_sheet_render(const float* wave, long long ld, const long long* lens, int L, const float* power, const int32_t* nframes,
+                    int F, int B, const float* thresholds, const unsigned char* cmap, unsigned bg, unsigned paper, unsigned ink,
+                    int cols, int Hw, int gutter, unsigned char* img, int H, int W, void* stream);
+
 /* ---- Conv2DLSTMCell (reference cells.py:4-103: convolutional LSTM with peepholes and TF layer normalisation) ----------
  * Pointwise / normalisation pieces (csrc/convlstm.hip); the convolution runs on ag_conv1d_engine, one launch per kernel row.
  * Every map is [H, B, C, W] contiguous (rows x batch = the 1-D engine's batch axis, W = its time axis); peephole weights
