@@ -3,6 +3,7 @@
 // MFMA product, and the dynamic-time-warping total between two batches of cepstral sequences.  Both are fp32 whatever
 // ag_set_precision says, use no atomics and add in a fixed order: two runs give the same bits.
 #include "common.h"
+#include "dtw_parts.h"
 
 // ------------------------------------------------------------------------------------------
 // ag_melcep_frames.  Framing, window and the folded transform are those of ag_ltas_power (evalstats.hip):
@@ -196,84 +197,29 @@ extern "C" int ag_melcep_frames(const float* x, int64_t ldx, const int64_t* lens
 }
 
 // ------------------------------------------------------------------------------------------
-// ag_dtw_cost: one workgroup per pair of sequences, thread i owns row i of the cost matrix (frame i of sequence a, its 12
-// coefficients in registers; sequence b's sit in LDS) and walks the n + m - 1 anti-diagonals: at step s it is at column
-// j = s - i.  Of the three predecessors, D(i, j-1) is the thread's own previous value; D(i-1, j) is thread i-1's value of
-// the previous step and D(i-1, j-1) its value of the step before - what this thread received one step earlier.  So a step
-// costs one shuffle; lane 0 of a wave takes its neighbour's value from LDS, where lane 63 of every wave leaves it (two
-// slots in turn, so one barrier per step orders the write of step s, its read in step s + 1 and the overwrite in s + 2).
-// The trip count n + m - 1 is the same for every thread of the workgroup and no thread leaves before the last barrier.
-// Rows are always those of sequence a: min is commutative and the local cost is the same sum of the same squares either
-// way, so dtw(a, b) and dtw(b, a) have the same bits without a choice of sides.
+// ag_dtw_cost: one workgroup per pair of sequences, rows those of sequence a; the recursion is dtw_parts.h's workgroup sweep.
+// Sequence b's LDS is static and sized for the capacity limit, whatever the lengths.
 // ------------------------------------------------------------------------------------------
-#define DT_MAX 1024
-#define DT_Q 12              // columns 1..12 of a 16-float row
-#define DT_ROW 16
-
 __global__ __launch_bounds__(1024) void dtw_cost_kernel(const float* __restrict__ ca, const int32_t* __restrict__ nfa,
                                                         const float* __restrict__ cb, const int32_t* __restrict__ nfb,
                                                         float* __restrict__ out, int Fa, int Fb) {
-  __shared__ __attribute__((aligned(16))) float sb[DT_MAX * DT_Q];
+  __shared__ __attribute__((aligned(16))) float sb[DTW_MAX * DTW_Q];
   __shared__ float edge[2][16];
-  const int b = blockIdx.x, i = threadIdx.x, lane = i & 63, w = i >> 6;
-  const int n = min(max(nfa ? nfa[b] : Fa, 1), Fa), m = min(max(nfb ? nfb[b] : Fb, 1), Fb);
-  {
-    const float* src = cb + (int64_t)b * Fb * DT_ROW;
-    for (int e = i; e < m * DT_Q; e += blockDim.x) {
-      const int j = e / DT_Q, q = e - j * DT_Q;
-      sb[e] = src[j * DT_ROW + 1 + q];
-    }
-  }
-  float a[DT_Q];
-  {
-    const float* src = ca + ((int64_t)b * Fa + min(i, n - 1)) * DT_ROW + 1;          // (idle threads: a row that exists)
-#pragma unroll
-    for (int q = 0; q < DT_Q; ++q) a[q] = src[q];
-  }
+  const int b = blockIdx.x, i = threadIdx.x;
+  const int n = dtw_count(nfa, b, Fa), m = dtw_count(nfb, b, Fb);
+  dtw_fill_cols(sb, cb, b, Fb, m, i, blockDim.x);
+  float a[DTW_Q];
+  dtw_load_row(a, ca, b, Fa, i, n);
   __syncthreads();
-  const float inf = __builtin_inff();
-  float cur = inf, diag = inf;
-  const int steps = n + m - 1;
-  for (int s = 0; s < steps; ++s) {
-    float up = __shfl_up(cur, 1, 64);
-    if (lane == 0 && w > 0 && s > 0) up = edge[(s - 1) & 1][w - 1];
-    const int j = s - i;
-    if (i < n && j >= 0 && j < m) {
-      const f32x4* r = reinterpret_cast<const f32x4*>(sb + j * DT_Q);
-      float ss = 0.f;
-#pragma unroll
-      for (int v = 0; v < 3; ++v) {
-        const f32x4 bv = r[v];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float df = a[4 * v + q] - bv[q];
-          ss = fmaf(df, df, ss);
-        }
-      }
-      const float d = sqrtf(ss);
-      float best;
-      if (i == 0 && j == 0) {
-        best = d + d;
-      } else {
-        best = inf;
-        if (i > 0) best = up + d;
-        if (j > 0) best = fminf(best, cur + d);
-        if (i > 0 && j > 0) best = fminf(best, diag + (d + d));
-      }
-      cur = best;
-    }
-    diag = up;
-    if (lane == 63) edge[s & 1][w] = cur;
-    __syncthreads();
-  }
+  const float cur = dtw_sweep_wg(a, sb, edge, i, n, m);
   if (i == n - 1) out[b] = cur;
 }
 
 extern "C" int ag_dtw_cost(const float* cep_a, const int32_t* nf_a, const float* cep_b, const int32_t* nf_b, float* out,
                            int B, int Fa, int Fb, void* stream) {
   AG_REQUIRE(cep_a && cep_b && out && B > 0 && Fa > 0 && Fb > 0, "ag_dtw_cost: bad args");
-  AG_REQUIRE(Fa <= DT_MAX && Fb <= DT_MAX, "ag_dtw_cost: sequences of up to %d frames (got capacities %d, %d)", DT_MAX, Fa,
-             Fb);
+  AG_REQUIRE(Fa <= DTW_MAX && Fb <= DTW_MAX, "ag_dtw_cost: sequences of up to %d frames (got capacities %d, %d)", DTW_MAX,
+             Fa, Fb);
   ag_note_kernel("dtw_cost_kernel");
   hipLaunchKernelGGL(dtw_cost_kernel, dim3(B), dim3(ag_roundup(Fa, AG_WAVE)), 0, (hipStream_t)stream, cep_a, nf_a, cep_b,
                      nf_b, out, Fa, Fb);
