@@ -242,15 +242,20 @@ class WNGroup(object):
         self._dws_flat.zero_()
         return list(self._dws)
 
-    def backward(self, dws):
-        """dws[i]: gradient wrt the materialised w of item i (same shape as v), or None.
-        Returns the flat list [dv0, dg0, dv1, dg1, ...]."""
+    def backward(self, dws, needs=None):
+        """dws[i]: gradient wrt the materialised w of item i (same shape as v), or None.  ``needs``: the calling Function's
+        ``needs_input_grad`` for [v0, g0, v1, g1, ...] - what required a gradient when the FORWARD ran.  A tensor takes a
+        gradient only if it did then (a forward under ``frozen`` leaves its ``.grad`` untouched even when other tensors of
+        the group train and the flag is back on by the time of the backward) and still does now (a backward under
+        ``losses.only_stopper_trains``).  Returns the flat list [dv0, dg0, dv1, dg1, ...]."""
         ents, outs = [], []
-        for it, dw in zip(self.items, dws):
-            if dw is None or not (it['v'].requires_grad or it['g'].requires_grad):
-                outs += [None, None]        # no gradient arrived / tensor frozen (e.g. stopper-only backward)
+        for i, (it, dw) in enumerate(zip(self.items, dws)):
+            nv, ng = (True, True) if needs is None else (bool(needs[2 * i]), bool(needs[2 * i + 1]))
+            if dw is None or not (nv or ng) or not (it['v'].requires_grad or it['g'].requires_grad):
+                outs += [None, None]        # no gradient arrived / tensor frozen (at forward time, or now: stopper-only backward)
                 continue
-            tv, tg = grad_target(it['v']), grad_target(it['g'])
+            # (frozen in part: the gradients go back as tensors and autograd drops the one nobody asked for)
+            tv, tg = grad_target(it['v']) if nv else None, grad_target(it['g']) if ng else None
             if tv is not None and tg is not None:
                 ents.append(dict(v=it['v'].data, g=it['g'].data.view(-1), dw=dw, dv=tv, dg=tg.view(-1),
                                  accumulate=True))

@@ -136,7 +136,7 @@ class GTrunkFn(torch.autograd.Function):
         dslab = torch.empty_like(slab)
         with K.deferred_reduces():      # every weight-gradient / bias-sum second stage of this backward in ONE launch
             GTrunkFn._backward_layers(trunk, prep, slab, hids, dy, dslab, dws, wg, ctot)
-        grads = trunk.group.backward(dws) if wg else [None] * (2 * len(trunk.group.items))
+        grads = trunk.group.backward(dws, ctx.needs_input_grad[2:]) if wg else [None] * (2 * len(trunk.group.items))
         dx0 = dslab[:, 0, :] if ctx.needs_input_grad[0] else None      # (a view: the front's backward reads it in place)
         return (dx0, None) + tuple(grads)
 
@@ -238,7 +238,7 @@ class DConvStackFn(torch.autograd.Function):
                     d = dx
                 else:
                     d = None
-        grads = stack.group.backward(dws) if wg else [None] * (2 * len(stack.group.items))
+        grads = stack.group.backward(dws, ctx.needs_input_grad[3:]) if wg else [None] * (2 * len(stack.group.items))
         dx0 = d.view(B, L) if (ctx.needs_input_grad[0] and d is not None) else None
         return (dx0, None, None) + tuple(grads)
 
@@ -406,7 +406,7 @@ class DHeadFn(torch.autograd.Function):
                     if i > 0:
                         K.act_bwd(dprev, acts[i], dprev, ACT_LEAKY)
                 da = dprev
-        grads = head.group.backward(dws) if wg else [None] * (2 * len(head.group.items))
+        grads = head.group.backward(dws, ctx.needs_input_grad[2:]) if wg else [None] * (2 * len(head.group.items))
         return (da if ctx.needs_input_grad[0] else None, None) + tuple(grads)
 
 

@@ -215,12 +215,21 @@ class LSTMSeqFn(torch.autograd.Function):
             if need_ds:
                 K.gemm(dgsums[d], w_ih[:, Fx:], dstatic, beta=1.0)
         outs = [] if wg else [None] * (4 * ndir)
-        tgs = [[grad_target(p_) for p_ in ctx.params[4 * d:4 * d + 4]] for d in range(ndir)] if wg else []
+        # a parameter takes a gradient only if it required one when the FORWARD ran (needs_input_grad: a forward under
+        # common.frozen leaves its .grad untouched whatever the flag says by now); a direction none of whose parameters
+        # did is skipped
+        needs = [[n_ and p_.requires_grad for n_, p_ in zip(ctx.needs_input_grad[4 + 4 * d:8 + 4 * d], ctx.params[4 * d:4 * d + 4])]
+                 for d in range(ndir)]          # (... and still does now: a backward under a freeze)
+        tgs = [[grad_target(p_) if n_ else None for p_, n_ in zip(ctx.params[4 * d:4 * d + 4], needs[d])]
+               for d in range(ndir)] if wg else []
         # every parameter gradient goes straight into ``.grad``: nothing reads it before the optimiser, so the second
         # stages of the split-K products and column sums below may wait for the enclosing scope's ONE launch
-        direct_all = wg and all(t_ is not None for tg in tgs for t_ in tg)
+        direct_all = wg and all(t_ is not None for tg, nd_ in zip(tgs, needs) if any(nd_) for t_ in tg)
         with (K.deferred_reduces() if direct_all else contextlib.nullcontext()):
             for d in range(ndir if wg else 0):
+                if not any(needs[d]):
+                    outs += [None, None, None, None]
+                    continue
                 w_ih, w_hh, tg = w[4 * d], w[4 * d + 1], tgs[d]
                 direct = all(t_ is not None for t_ in tg)
                 if direct:      # accumulate straight into .grad
@@ -477,7 +486,7 @@ class GFrontFn(torch.autograd.Function):
             dws = [None] * len(items)
             dws[4 * nl + 2], dws[4 * nl + 3] = _zeros_like_list([items[4 * nl + 2]['v'], items[4 * nl + 3]['v']])
             _stop_head_grads(ds, hs[-1].view(T * B, S), dws, 4 * nl + 2)
-            return (None, None) + tuple(front.group.backward(dws))
+            return (None, None) + tuple(front.group.backward(dws, ctx.needs_input_grad[2:]))
         dws = front.group.zero_dws() if wg else None
         # (the persistent launch takes frame sizes the fused per-frame step does not: any multiple of 8 up to its panel width)
         persist = nl == 1 and _one_launch(K.gfront_bwd_persist_ok, T, wx, B, S, fs, dev)
@@ -522,7 +531,7 @@ class GFrontFn(torch.autograd.Function):
             dzc = torch.empty(T * B, Fz, device=dev)
             K.gemm(dgs[0].view(T * B, 4 * S), lw[0][0][:, fs:], dzc)
             dzc = dzc.view(T, B, Fz)
-        grads = front.group.backward(dws) if wg else [None] * (2 * len(front.group.items))
+        grads = front.group.backward(dws, ctx.needs_input_grad[2:]) if wg else [None] * (2 * len(front.group.items))
         return (dzc, None) + tuple(grads)
 
 
@@ -640,7 +649,7 @@ class GRUFrontFn(torch.autograd.Function):
             dzc = torch.empty(T * B, Fz, device=dev)
             K.gemm(dgi2, w_ih[:, fs:], dzc)
             dzc = dzc.view(T, B, Fz)
-        return (dzc, None) + tuple(front.group.backward(dws) if wg else [None] * (2 * len(front.group.items)))
+        return (dzc, None) + tuple(front.group.backward(dws, ctx.needs_input_grad[2:]) if wg else [None] * (2 * len(front.group.items)))
 
 
 # --------------------------------------------------------------------------------------
