@@ -190,6 +190,14 @@ SIGNATURES = {
     'ag_dtw_align_ws': (i64, [C.c_int, C.c_int]),
     'ag_dtw_align': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]),
     'ag_dtw_align_forward': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]),
+    'ag_pitch_window': (C.c_int, []),
+    'ag_pitch_tmin': (C.c_int, []),
+    'ag_pitch_tmax': (C.c_int, []),
+    'ag_pitch_nccf_width': (C.c_int, []),
+    'ag_pitch_tile': (C.c_int, []),
+    'ag_pitch_path_words': (C.c_int, []),
+    'ag_pitch_frames': (C.c_int, [vp, i64, vp, f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    'ag_pitch_path_accum': (C.c_int, [vp, vp, vp, vp, vp, f32, vp, C.c_int, C.c_int, C.c_int, vp]),
     'ag_resample_ok': (C.c_int, [C.c_int] * 5),
     'ag_resample_poly': (C.c_int, [vp, C.c_int, C.c_int, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, vp, i64, i64, i64,
                                    C.c_int, vp]),

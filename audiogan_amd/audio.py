@@ -12,7 +12,11 @@ numpy (the path without a GPU, and the reference of every test), ``resample`` ru
 Where the words are: ``activity`` finds the active stretches of rows of 8 kHz samples by short-time energy (the reference cuts
 words by a forced alignment, preprocess-fisher.py:145-146, or keeps loud windows, preprocess.py:25-27) - ``activity_rule`` is
 the rule on the host, ``activity64`` the path without a GPU, and on the device ``kernels.frame_power`` and
-``kernels.activity_segments`` (ag_frame_power, ag_activity_segments) run it."""
+``kernels.activity_segments`` (ag_frame_power, ag_activity_segments) run it.
+
+Pitch: ``pitch64`` is the rule of ``kernels.pitch_frames`` (ag_pitch_frames) in float64 numpy - per frame the first strong peak
+of the normalised cross-correlation - the arbiter of its tests and the path without a GPU (``evaluate.pitch_cents`` refines
+its lags to cents)."""
 import math
 import struct
 import warnings
@@ -462,3 +466,74 @@ def activity(y, lens=None, sr=8000, top_db=40.0, floor_db=-80.0, win_ms=25.0, ho
         seg, _, _ = K.activity_segments(*args, K=int(count.max()))
     seg = seg.cpu().numpy()
     return [None if count[b] < 0 else seg[b, :count[b]].copy() for b in range(B)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# pitch candidates per frame: the rule of kernels.pitch_frames (ag_pitch_frames) in float64
+# ----------------------------------------------------------------------------------------------------------------------
+PITCH_W, PITCH_HOP, PITCH_TMIN, PITCH_TMAX, PITCH_NCCF = 256, 128, 20, 127, 112
+
+
+def pitch_frame_count(n):
+    """frames of a clip of n samples: those of ``kernels.melcep_frames``"""
+    n = int(n)
+    return (n - PITCH_W) // PITCH_HOP + 1 if n >= PITCH_W else 1
+
+
+def pitch_rule64(phi, octf):
+    """phi [.., 110] float64, the normalised cross-correlation at lags 19..128 -> the column (lag - 19) of the SMALLEST lag
+    in 20..127 that is a local maximum (>= both neighbours) and reaches octf times the largest phi of 20..127; 0: the
+    largest is not positive, or no lag qualifies"""
+    mid, left, right = phi[..., 1:-1], phi[..., :-2], phi[..., 2:]
+    M = mid.max(-1)
+    ok = (mid >= left) & (mid >= right) & (mid >= octf * M[..., None]) & (M[..., None] > 0.0)
+    return np.where(ok.any(-1), ok.argmax(-1) + 1, 0)
+
+
+def pitch64(wave, lens=None, octf=0.9, center=True):
+    """the rule of ``kernels.pitch_frames`` in float64 numpy: the arbiter of its tests and the path without a GPU.  ``wave``
+    [L] or [B, L], ``lens``: samples per row (default L) -> (lag [B, F] int32, peak [B, F, 4], nccf [B, F, 112], nframes [B]
+    int32), F the frame count of L samples; rows at or past a clip's frame count hold zeros.  Frame j is samples 128 j ..
+    128 j + 383 (zeros at and past the clip's length, which is never read); ``center``: the mean of the segment's valid
+    samples is subtracted from them.  phi(tau) = r / sqrt(e0 e(tau)) where that is positive, else 0, over the 256-sample
+    window, tau = 19..128; the lag is ``pitch_rule64``'s; peak = phi(lag - 1), phi(lag), phi(lag + 1), e0 / 256.  ``octf`` is
+    taken at its fp32 value, the one the kernel receives."""
+    y, is_t, B, L, ln = _rows_and_lens(wave, lens)
+    y = y.detach().cpu().numpy() if is_t else y
+    octf = float(np.float32(octf))
+    if not 0.0 < octf <= 1.0:
+        raise ValueError('audiogan_amd: pitch64 takes octf in (0, 1], got %r' % (octf,))
+    seg_len, nlag = PITCH_W + PITCH_HOP, PITCH_TMAX - PITCH_TMIN + 3
+    F = pitch_frame_count(L)
+    lag = np.zeros((B, F), dtype=np.int32)
+    peak, nccf = np.zeros((B, F, 4)), np.zeros((B, F, PITCH_NCCF))
+    nframes = np.array([pitch_frame_count(n) for n in ln], dtype=np.int32)
+    t = np.arange(seg_len)
+    for b in range(B):
+        n, nf = int(ln[b]), int(nframes[b])
+        buf = np.zeros((nf - 1) * PITCH_HOP + seg_len)
+        m = min(n, len(buf))
+        buf[:m] = np.asarray(y[b, :m], dtype=np.float64)
+        seg = buf[np.arange(nf)[:, None] * PITCH_HOP + t[None, :]]                       # [nf, 384]
+        if center:
+            valid = (np.arange(nf)[:, None] * PITCH_HOP + t[None, :]) < n
+            nv = valid.sum(1)
+            mean = np.where(nv > 0, seg.sum(1) / np.maximum(nv, 1), 0.0)                 # (the padding adds zeros)
+            seg = np.where(valid, seg - mean[:, None], 0.0)
+        head = seg[:, :PITCH_W]
+        e0 = (head * head).sum(1)
+        phi = np.zeros((nf, nlag))
+        for k in range(nlag):
+            tail = seg[:, PITCH_TMIN - 1 + k:PITCH_TMIN - 1 + k + PITCH_W]
+            den = e0 * (tail * tail).sum(1)
+            pos = den > 0.0
+            phi[pos, k] = (head * tail).sum(1)[pos] / np.sqrt(den[pos])
+        col = pitch_rule64(phi, octf)
+        rows = np.arange(nf)
+        found = col > 0
+        lag[b, :nf] = np.where(found, col + PITCH_TMIN - 1, 0)
+        for d in range(3):
+            peak[b, :nf, d] = np.where(found, phi[rows, np.clip(col - 1 + d, 0, nlag - 1)], 0.0)
+        peak[b, :nf, 3] = e0 / float(PITCH_W)
+        nccf[b, :nf, :nlag] = phi
+    return lag, peak, nccf, nframes

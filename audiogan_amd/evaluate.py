@@ -23,6 +23,7 @@ What a pass measures (``run``), per held-out minibatch, without instance noise a
     aligned=True   dtw_cost(melcep_frames(fake), melcep_frames(real), computed once)  -> mcd_db
     crossed=True   dtw_pairs(every fake's cepstra x every real clip's of the minibatch)  -> nn_db, cover_db, word_hit
     draws=k        k - 1 further fakes per word, dtw_pairs between the draws             -> div_db (beside real_div_db)
+    pitch=True     pitch_frames(fake), dtw_align instead of dtw_cost, pitch_path_accum   -> f0_rmse_cents, vuv_err, gpe
 
 ``ltas_db`` is the mean over all clips of sqrt(mean_k (dB_fake[k] - dB_real[k])^2), dB = 10 log10(P + 1e-10) over the 129 bins
 of ``kernels.ltas_power``; fake i and real clip i share their word.  The statistics are accumulated on the device
@@ -54,6 +55,22 @@ Zero means z does nothing.  Two real utterances of a word are some dB apart as w
 beside ``real_div_db``: the same mean over all pairs of held-out REAL clips that share a word, computed once when the
 evaluator is built (None when no word occurs twice).  The extra fakes get no critic pass.
 
+``pitch`` (off by default, needs ``aligned``) measures what the cepstra smooth away on purpose - the excitation.  13
+coefficients from 24 bands of a 256-point frame carry no harmonics and c0 is left out, so a fake that is whispered where the
+word is voiced, buzzes at one pitch or sits an octave off scores like a good one in ``mcd_db``.  ``kernels.pitch_frames``
+gives every frame (the cepstra's own framing) a pitch candidate: the normalised cross-correlation of the 256-sample window
+with its copy 19..128 samples later (400 Hz down to 63 Hz at 8 kHz), and of the local maxima within ``octf`` = 0.9 of the
+largest the one at the SMALLEST lag, which is what avoids octave errors.  ``pitch_cents`` refines the lag by a parabola and
+takes the logarithm, in float64: cents above 50 Hz, -1 where the frame is unvoiced (correlation below 0.5 or power below
+1e-6).  ``kernels.dtw_align`` returns the path of the recursion behind ``mcd_db`` with the bits of ``dtw_cost`` in its
+total, so with ``pitch`` on it replaces that launch and feeds both; ``kernels.pitch_path_accum`` adds up, over the path's
+cells, how many there are, how many have both frames voiced, how many differ in voicing, how many both-voiced ones are
+more than 20 % apart, and the squared F0 difference.  Pooled over the held-out set: ``f0_rmse_cents`` = sqrt(sum d^2 / both),
+``gpe`` = gross / both (both None while no cell has both frames voiced - an untrained generator), ``vuv_err`` = differing /
+cells, and ``voiced/fake``, ``voiced/real``, the share of voiced frames on each side.  Like ``mcd_db`` these are distances
+to ONE real take of the word: two speakers of a word differ in F0 by hundreds of cents, so only the trend over training on
+the fixed set says something.
+
 What the numbers do NOT say: the held-out clips are few and fixed, so the critic numbers are a trend, not an estimate with
 error bars; and a long-term average spectrum is blind to everything temporal - a sample can match it and still be
 unintelligible.  It answers "is the energy in the right bands", nothing more.
@@ -76,6 +93,9 @@ from .extras import feature_penalty_fused
 DB_FLOOR = 1e-10
 _ACC_D, _ACC_G, _PEN, _LTAS, _FRAMES, _MCD, _NN, _COVER, _HIT, _DIV, _WORDS = 0, 6, 12, 13, 14, 15, 16, 17, 18, 19, 20
 MCD_DB = 10.0 / math.log(10.0) * math.sqrt(2.0)          # the mel-cepstral distance's constant: natural-log cepstra -> dB
+# pitch=True: further words BEHIND the others - the five sums of kernels.pitch_path_accum, the fakes' voiced frames, their frames
+_PSUMS, _VOICED, _PFRAMES, _PITCH_WORDS = _WORDS, _WORDS + 5, _WORDS + 6, 7
+PITCH_SR, PITCH_REF_HZ = 8000.0, 50.0                    # cents are 1200 log2(F0 / 50 Hz) at the models' 8 kHz
 
 
 def power_db(p):
@@ -110,6 +130,60 @@ def _pair_db(total, nf_a, nf_b):
     return MCD_DB * total.double() / (nf_a + nf_b).double()
 
 
+def pitch_cents(lag, peak, vthr=0.5, pfloor=1e-6):
+    """lag [..] int32 and peak [.., 4] as ``kernels.pitch_frames`` (or ``audio.pitch64``) leaves them -> fp32 [..]: the frame's
+    F0 in cents above 50 Hz, or -1 where it is unvoiced.  Elementwise torch where the inputs live, in float64, stored as
+    fp32 (the logarithm and the refinement are taken here, not in the kernel).  Voiced: lag > 0, phi(lag) >= ``vthr`` and the
+    window's mean power e0 / 256 >= ``pfloor``.  The lag is refined by the parabola through phi(lag - 1), phi(lag),
+    phi(lag + 1): with den = phi- - 2 phi0 + phi+, delta = 0.5 (phi- - phi+) / den clamped to [-0.5, 0.5] when den < 0, else
+    0; cents = 1200 log2((8000 / (lag + delta)) / 50).  Every voiced value is above 380, so a negative value is the flag."""
+    lag = torch.as_tensor(lag)
+    p = torch.as_tensor(peak).to(lag.device).double()
+    pm, p0, pp, power = p[..., 0], p[..., 1], p[..., 2], p[..., 3]
+    voiced = (lag > 0) & (p0 >= vthr) & (power >= pfloor)
+    den = pm - 2.0 * p0 + pp
+    curved = den < 0
+    delta = torch.where(curved, (0.5 * (pm - pp) / torch.where(curved, den, torch.ones_like(den))).clamp(-0.5, 0.5),
+                        torch.zeros_like(den))
+    period = torch.where(voiced, lag.double() + delta, torch.ones_like(den))
+    cents = 1200.0 * torch.log2((PITCH_SR / period) / PITCH_REF_HZ)
+    return torch.where(voiced, cents, torch.full_like(cents, -1.0)).float()
+
+
+def pitch_path_sums64(pc_a, pc_b, lo, hi, nf_b=None, gross=None):
+    """the rule of ``kernels.pitch_path_accum`` in float64 numpy: pc_a [B, Fa], pc_b [B, Fb] cents (negative: unvoiced), lo /
+    hi [B, Fb] and nf_b [B] (None: Fb; clamped to [1, Fb]) -> float64 [B, 5]: over the cells (column j < nf_b[b], rows
+    lo[j]..hi[j], row indices clamped into [0, Fa - 1]) their number, those with both frames voiced, those whose voicing
+    differs, the both-voiced ones with |a - b| > gross, and the sum of (a - b)^2 over the both-voiced ones.  ``gross`` is
+    taken at its fp32 value (default: that of 1200 log2(1.2)).  Columns at or past the count are never read."""
+    tn = lambda v: v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)          # noqa: E731
+    pc_a, pc_b, lo, hi = tn(pc_a), tn(pc_b), tn(lo), tn(hi)
+    gross = float(np.float32(K.PITCH_GROSS if gross is None else gross))
+    B, Fa, Fb = pc_a.shape[0], pc_a.shape[1], pc_b.shape[1]
+    out = np.zeros((B, 5))
+    for b in range(B):
+        m = Fb if nf_b is None else max(1, min(int(tn(nf_b)[b]), Fb))
+        for j in range(m):
+            r0, r1 = (max(0, min(int(v), Fa - 1)) for v in (lo[b, j], hi[b, j]))
+            a, vb = pc_a[b, r0:r1 + 1].astype(np.float64), float(pc_b[b, j])
+            both = (a >= 0) & (vb >= 0)
+            d = a[both] - vb
+            out[b] += (len(a), both.sum(), ((a >= 0) != (vb >= 0)).sum(), (np.abs(d) > gross).sum(), (d * d).sum())
+    return out
+
+
+def pitch_scores(sums):
+    """[B, 5] sums of ``kernels.pitch_path_accum`` (tensor or array) -> dict of [B] float64 tensors: f0_rmse_cents = sqrt(sum d^2
+    / both) and gpe = gross / both (NaN where no cell has both frames voiced), vuv_err = differing / cells, cells"""
+    s = torch.as_tensor(sums).double()
+    cells, both, differ, far, ss = s.unbind(-1)
+    nan = torch.full_like(ss, float('nan'))
+    some = both > 0
+    safe = torch.where(some, both, torch.ones_like(both))
+    return dict(f0_rmse_cents=torch.where(some, (ss / safe).sqrt(), nan), vuv_err=differ / cells,
+                gpe=torch.where(some, far / safe, nan), cells=cells)
+
+
 def finish_scores(a):
     """the host's half of ``kernels.score_accum``: six words -> (loss, accuracy, mean, std)"""
     a0, a1, a2, a3, a4, a5 = (float(v) for v in a)
@@ -119,7 +193,7 @@ def finish_scores(a):
 
 class Evaluator(object):
     def __init__(self, g, d, e_g, e_d, heldout, batch_size, maxlen, device, batches=4, seed=0, ema=None, on_eval=None,
-                 path=None, aligned=False, crossed=False, draws=1):
+                 path=None, aligned=False, crossed=False, draws=1, pitch=False):
         """``heldout``: the validation loader ``dataset.dataloader`` returns (``next()`` -> [epoch, batch, samples, lengths,
         keys, cseq, clen]) or a list of such minibatches; ``batches`` of them are taken NOW (see the module text: build the
         evaluator before the training loader's first ``next()`` when this is a loader).  ``ema``: an ``optim.EMA`` - the pass
@@ -127,18 +201,22 @@ class Evaluator(object):
         result is appended there as one JSON line with ``kind: 'E'``.  ``aligned``: also measure ``mcd_db``, the
         mel-cepstral distance of every fake along its time-warping path to the real clip of the same word (module text)
         - the real clips' cepstra are computed now and kept.  ``crossed`` / ``draws`` (both need ``aligned``): also measure
-        ``nn_db``, ``cover_db``, ``word_hit`` and ``word_hit/chance`` / ``div_db`` and ``real_div_db`` (module text)."""
+        ``nn_db``, ``cover_db``, ``word_hit`` and ``word_hit/chance`` / ``div_db`` and ``real_div_db`` (module text).
+        ``pitch`` (needs ``aligned``): also measure ``f0_rmse_cents``, ``vuv_err``, ``gpe``, ``voiced/fake`` and
+        ``voiced/real`` along the time-warping path (module text) - the real clips' cents are computed now and kept."""
         self.g, self.d, self.e_g, self.e_d = g, d, e_g, e_d
         self.B, self.maxlen, self.dev = int(batch_size), maxlen, torch.device(device)
         self.ema, self.on_eval, self.path = ema, on_eval, path
         fs = g._frame_size
         self.nframes = (maxlen + fs - 1) // fs
         self.L = self.nframes * fs
-        self.aligned, self.crossed, self.draws = bool(aligned), bool(crossed), int(draws)
+        self.aligned, self.crossed, self.draws, self.pitch = bool(aligned), bool(crossed), int(draws), bool(pitch)
         if self.draws < 1 or self.draws != draws:
             raise ValueError('Evaluator(draws=%r): a whole number of draws per word, 1 or more' % (draws,))
         if (self.crossed or self.draws > 1) and not self.aligned:
             raise ValueError('Evaluator(crossed=%r, draws=%r) compares cepstra: it needs aligned=True' % (crossed, draws))
+        if self.pitch and not self.aligned:
+            raise ValueError('Evaluator(pitch=%r) compares F0 along the cepstra\'s path: it needs aligned=True' % (pitch,))
         if self.aligned and K.lt_frames(self.L) > K.DTW_MAX_FRAMES:
             raise ValueError('Evaluator(aligned=True): clips of %d samples have %d frames; kernels.dtw_cost takes at most %d'
                              % (self.L, K.lt_frames(self.L), K.DTW_MAX_FRAMES))
@@ -160,6 +238,8 @@ class Evaluator(object):
             if self.aligned:
                 nf = torch.empty(self.B, dtype=torch.int32, device=self.dev)
                 self.set[-1].update(real_cep=K.melcep_frames(real, real_len, nframes=nf), real_nf=nf)
+            if self.pitch:
+                self.set[-1].update(real_cents=pitch_cents(*K.pitch_frames(real, real_len)))
         self.clips = self.B * batches
         self._chance = self.real_div_db = None
         if self.crossed or self.draws > 1:
@@ -186,7 +266,15 @@ class Evaluator(object):
                 ia, ib = (self._up(np.array(c, dtype=np.int32), torch.int32) for c in zip(*ij))
                 tot = K.dtw_pairs(cep, nf, cep, nf, ia, ib)
                 self.real_div_db = float(_pair_db(tot, nf[ia.long()], nf[ib.long()]).mean())
-        self._buf = torch.zeros(_WORDS, dtype=torch.float64, device=self.dev)
+        self._buf = torch.zeros(_WORDS + (_PITCH_WORDS if self.pitch else 0), dtype=torch.float64, device=self.dev)
+        self.voiced_real = None
+        if self.pitch:
+            F = K.lt_frames(self.L)
+            self._frame = torch.arange(F, device=self.dev)
+            # the decisions of dtw_align, for the widest fake a pass can meet: allocated once
+            self._align_ws = torch.empty(max(self.B * K.dtw_align_ws(F, F), 4) // 4, dtype=torch.int32, device=self.dev)
+            on = sum(int(((mb['real_cents'] >= 0) & (self._frame[None, :] < mb['real_nf'][:, None])).sum()) for mb in self.set)
+            self.voiced_real = on / float(sum(int(mb['real_nf'].sum()) for mb in self.set))
 
     def _up(self, a, dtype):
         return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(dtype).to(self.dev)
@@ -234,10 +322,24 @@ class Evaluator(object):
                 if self.aligned:
                     nf = torch.empty(self.B, dtype=torch.int32, device=self.dev)
                     cep = K.melcep_frames(fake, fake_len, nframes=nf)
-                    dtw = K.dtw_cost(cep, nf, mb['real_cep'], mb['real_nf'])
+                    if self.pitch:
+                        # the total has dtw_cost's bits (the same recursion), so one launch feeds mcd_db and the path
+                        dtw, lo, hi = K.dtw_align(cep, nf, mb['real_cep'], mb['real_nf'], workspace=self._align_ws)
+                    else:
+                        dtw = K.dtw_cost(cep, nf, mb['real_cep'], mb['real_nf'])
                     buf[_MCD] += (dtw.double() / (nf + mb['real_nf']).double()).sum()
                     if parts:
                         kept[-1].update(cep=cep, nf=nf, real_cep=mb['real_cep'], real_nf=mb['real_nf'], dtw=dtw)
+                if self.pitch:
+                    lag, peak = K.pitch_frames(fake, fake_len)
+                    cents = pitch_cents(lag, peak)
+                    sums = K.pitch_path_accum(cents, mb['real_cents'], lo, hi, mb['real_nf'])
+                    buf[_PSUMS:_PSUMS + 5] += sums.double().sum(0)
+                    buf[_VOICED] += ((cents >= 0) & (self._frame[None, :cents.size(1)] < nf[:, None])).sum()
+                    buf[_PFRAMES] += nf.sum()
+                    if parts:
+                        kept[-1].update(lag=lag, peak=peak, cents=cents, real_cents=mb['real_cents'], lo=lo, hi=hi,
+                                        pitch_sums=sums)
                 if self.crossed:
                     cross = K.dtw_pairs(cep, nf, mb['real_cep'], mb['real_nf'])
                     nn, cover, hit = _crossed_sums(_pair_db(cross, nf[:, None], mb['real_nf'][None, :]), mb['same'])
@@ -272,6 +374,12 @@ class Evaluator(object):
         res['frames/mean'] = host[_FRAMES] / self.clips
         if self.aligned:
             res['mcd_db'] = MCD_DB * host[_MCD] / self.clips
+        if self.pitch:
+            cells, both, differ, far, ss = host[_PSUMS:_PSUMS + 5]
+            res['f0_rmse_cents'] = math.sqrt(ss / both) if both > 0 else None
+            res['vuv_err'] = differ / cells
+            res['gpe'] = far / both if both > 0 else None
+            res['voiced/fake'], res['voiced/real'] = host[_VOICED] / host[_PFRAMES], self.voiced_real
         if self.crossed:
             res['nn_db'], res['cover_db'] = host[_NN] / self.clips, host[_COVER] / self.clips
             res['word_hit'], res['word_hit/chance'] = host[_HIT] / self.clips, self._chance
@@ -303,6 +411,27 @@ def aligned_distance(wave_a, len_a, wave_b, len_b):
     cep_a = K.melcep_frames(wave_a, len_a, nframes=nf_a)
     cep_b = K.melcep_frames(wave_b, len_b, nframes=nf_b)
     return MCD_DB * K.dtw_cost(cep_a, nf_a, cep_b, nf_b).double() / (nf_a + nf_b).double()
+
+
+def pitch_distance(wave_a, len_a, wave_b, len_b, vthr=0.5, pfloor=1e-6):
+    """wave_a [B, La], wave_b [B, Lb] with their lengths as ``aligned_distance`` takes them -> dict of [B] float64 tensors, per
+    pair along the time-warping path of their cepstra (a's frames the rows): ``f0_rmse_cents`` (the root mean square F0
+    difference over the cells with both frames voiced; NaN where there is none), ``vuv_err`` (the share of cells whose
+    voicing differs), ``gpe`` (the share of both-voiced cells more than 20 % apart; NaN as above) and ``cells``.  What
+    ``Evaluator(aligned=True, pitch=True)`` pools over the held-out set (module text); two ``melcep_frames``, two
+    ``pitch_frames``, one ``dtw_align`` and one ``pitch_path_accum`` launch."""
+    for w in (wave_a, wave_b):
+        if K.lt_frames(w.size(1)) > K.DTW_MAX_FRAMES:
+            raise ValueError('pitch_distance: clips of %d samples have more than %d frames' % (w.size(1), K.DTW_MAX_FRAMES))
+    B = wave_a.size(0)
+    nf_a = torch.empty(B, dtype=torch.int32, device=wave_a.device)
+    nf_b = torch.empty(B, dtype=torch.int32, device=wave_a.device)
+    cep_a = K.melcep_frames(wave_a, len_a, nframes=nf_a)
+    cep_b = K.melcep_frames(wave_b, len_b, nframes=nf_b)
+    _, lo, hi = K.dtw_align(cep_a, nf_a, cep_b, nf_b)
+    pc_a = pitch_cents(*K.pitch_frames(wave_a, len_a), vthr=vthr, pfloor=pfloor)
+    pc_b = pitch_cents(*K.pitch_frames(wave_b, len_b), vthr=vthr, pfloor=pfloor)
+    return pitch_scores(K.pitch_path_accum(pc_a, pc_b, lo, hi, nf_b))
 
 
 def aligned_distance_matrix(wave_a, len_a, wave_b, len_b):

@@ -66,6 +66,7 @@ def parser():
     own.add_argument('--eval-batches', type=int, default=4)
     own.add_argument('--aligned', action='store_true', help='evaluation: add the DTW-aligned mel-cepstral distance')
     own.add_argument('--crossed', action='store_true', help='evaluation: add diversity and word retrieval')
+    own.add_argument('--pitch', action='store_true', help='evaluation: add F0 and voicing error along the aligned path')
     own.add_argument('--seed', type=int, default=0)
     shape = ap.add_argument_group('network shapes the reference fixes in its source')
     shape.add_argument('--gstruct', type=_struct, default=None, metavar='K,S,HID,OUT;..', help="the generator's conv stack")
@@ -100,6 +101,10 @@ def parse(argv=None):
                  % (a.sheet_every, a.sample_every))
     if (a.aligned or a.crossed) and not a.eval_every:
         ap.error('--aligned / --crossed belong to the held-out evaluation: set --eval-every')
+    if a.pitch and not a.eval_every:
+        ap.error('--pitch belongs to the held-out evaluation: set --eval-every')
+    if a.pitch and not a.aligned:
+        ap.error('--pitch compares F0 along the time-warping path of the cepstra: set --aligned')
     if a.eval_every and a.eval_batches < 1:
         ap.error('--eval-batches %d: at least one held-out minibatch' % a.eval_batches)
     if a.loaditerations and not (a.modelnameload or a.modelnamesave):
@@ -155,7 +160,8 @@ def build(a):
     ev = None
     if a.eval_every:
         ev = evaluate.Evaluator(g, d, e_g, e_d, heldout, B, maxlen, dev, batches=len(heldout), seed=a.seed, ema=ema,
-                                path=(a.summary + '.eval') if a.summary else None, aligned=a.aligned, crossed=a.crossed)
+                                path=(a.summary + '.eval') if a.summary else None, aligned=a.aligned, crossed=a.crossed,
+                                pitch=a.pitch)
     sdir = _sample_dir(a)
     sheets = sheet.SheetWriter(sdir, every=a.sheet_every or 1, cols=a.sheet_cols) if sdir is not None else None
     sampling = bool(a.sample_every or a.audio_every)

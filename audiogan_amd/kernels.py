@@ -2169,6 +2169,64 @@ def dtw_align(cep_a, nf_a, cep_b, nf_b, total=None, lo=None, hi=None, workspace=
 
 
 # ------------------------------------------------------------------------------------
+# pitch measures (evaluate.Evaluator(aligned=True, pitch=True), evaluate.pitch_distance): pitch candidates per frame, the sums
+# along the alignment path.  Not under @_timed, as dtw_align is not: tests/test_launch_layer.py pins the timed set;
+# tools/prof_pitch.py times them with device events and the library names both launches to ag_last_kernel.
+# ------------------------------------------------------------------------------------
+PITCH_W, PITCH_TMIN, PITCH_TMAX = int(lib.ag_pitch_window()), int(lib.ag_pitch_tmin()), int(lib.ag_pitch_tmax())
+PITCH_LAG0 = PITCH_TMIN - 1                                # the lag of nccf's column 0
+PITCH_LAGS = PITCH_TMAX - PITCH_TMIN + 3                   # lags 19..128
+PITCH_NCCF = int(lib.ag_pitch_nccf_width())                # floats per nccf row: the lags and two zero columns
+PITCH_TILE = int(lib.ag_pitch_tile())                      # frames one workgroup of ag_pitch_frames takes
+PITCH_PATH_WORDS = int(lib.ag_pitch_path_words())          # cells, both voiced, voicing differs, gross, sum d^2
+PITCH_GROSS = 1200.0 * float(np.log2(1.2))                 # cents: the usual 20 % gross-error threshold
+assert (PITCH_W, PITCH_TMIN, PITCH_TMAX, PITCH_LAGS, PITCH_NCCF, PITCH_PATH_WORDS) == (256, 20, 127, 110, 112, 5)
+
+
+def pitch_frames(x, lens, octf=0.9, center=True, lag=None, peak=None, nccf=None, nframes=None):
+    """x [B, L] and lens as ``melcep_frames`` takes them, on ITS framing (frame j starts at sample 128 j; F = lt_frames(L))
+    -> (lag [B, F] int32, peak [B, F, 4] fp32).  Per frame the normalised cross-correlation phi(tau) of the 256-sample
+    window with its copy tau samples later, tau = 19..128, fp32 fmaf chains in ascending order; ``center``: the mean of the
+    segment's valid samples is subtracted first.  lag = the SMALLEST tau in 20..127 that is a local maximum of phi and
+    reaches ``octf`` times the largest phi of that range (0: none); peak = phi(lag - 1), phi(lag), phi(lag + 1) and the
+    window's mean power e0 / 256.  ``nccf``: a [B, F, 112] tensor that receives phi(19..128) and two zero columns;
+    ``nframes``: an int32 [B] tensor that receives the frame counts.  Rows at or past a clip's frame count are not written
+    and samples at or past ``lens`` are never read (ag_pitch_frames: one launch; ``evaluate.pitch_cents`` refines)."""
+    _chk(x, 'x')
+    assert x.dim() == 2, tuple(x.shape)
+    B, L = x.shape
+    F = lt_frames(L)
+    if lag is None:
+        lag = torch.empty(B, F, dtype=torch.int32, device=x.device)
+    if peak is None:
+        peak = torch.empty(B, F, 4, dtype=torch.float32, device=x.device)
+    ld = _check_table([(x, 'x', (B, L), _PITCHED), (lens, 'lens', (B,), torch.int64), (lag, 'lag', (B, F), torch.int32),
+                       (peak, 'peak', (B, F, 4)), (nccf, 'nccf', (B, F, PITCH_NCCF)),
+                       (nframes, 'nframes', (B,), torch.int32)])
+    check(lib.ag_pitch_frames(_p(x), ld['x'], _p(lens), float(octf), int(bool(center)), _p(lag), _p(peak), _p(nccf),
+                              _p(nframes), B, L, _stream()), 'ag_pitch_frames')
+    return lag, peak
+
+
+def pitch_path_accum(pc_a, pc_b, lo, hi, nf_b=None, gross=None, out=None):
+    """pc_a [B, Fa] (the rows of the alignment), pc_b [B, Fb] (its columns): fp32 cents per frame, negative = unvoiced
+    (``evaluate.pitch_cents``); lo, hi int32 [B, Fb] and nf_b int32 [B] as ``dtw_align`` leaves and takes them -> out [B, 5]
+    fp32: over the path's cells (column j < nf_b[b], rows lo..hi) their number, those with both frames voiced, those whose
+    voicing differs, the both-voiced ones further apart than ``gross`` cents (default 1200 log2(1.2)), and the sum of
+    (a - b)^2 over the both-voiced ones.  Columns at or past the count are never read; at most 1024 frames a side
+    (ag_pitch_path_accum: one launch, one workgroup per pair)."""
+    assert pc_a.dim() == 2 and pc_b.dim() == 2, (tuple(pc_a.shape), tuple(pc_b.shape))
+    B, Fa, Fb = pc_a.size(0), pc_a.size(1), pc_b.size(1)
+    if out is None:
+        out = torch.empty(B, PITCH_PATH_WORDS, dtype=torch.float32, device=pc_a.device)
+    _check_table([(pc_a, 'pc_a', (B, Fa)), (pc_b, 'pc_b', (B, Fb)), (lo, 'lo', (B, Fb), torch.int32),
+                  (hi, 'hi', (B, Fb), torch.int32), (nf_b, 'nf_b', (B,), torch.int32), (out, 'out', (B, PITCH_PATH_WORDS))])
+    check(lib.ag_pitch_path_accum(_p(pc_a), _p(pc_b), _p(lo), _p(hi), _p(nf_b), float(PITCH_GROSS if gross is None else gross),
+                                  _p(out), B, Fa, Fb, _stream()), 'ag_pitch_path_accum')
+    return out
+
+
+# ------------------------------------------------------------------------------------
 # ingestion (audio.resample, ingest.build_store): polyphase resampling of ragged rows of PCM frames
 # ------------------------------------------------------------------------------------
 def resample_ok(L, M, taps, channels, kind):

@@ -854,6 +854,62 @@ int ag_dtw_align_forward(const float* cep_a, const int32_t* nf_a, const float* c
                          int32_t* lo, int32_t* hi, void* ws, int64_t ws_bytes, int B, int Fa, int Fb, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Pitch measures of the held-out evaluation (evaluate.Evaluator(aligned=True, pitch=True), evaluate.pitch_distance;
+ * csrc/pitch.hip): per-frame pitch candidates from the normalised cross-correlation, and the sums of F0 and voicing
+ * differences along the path of ag_dtw_align.  Both kernels are fp32 whatever ag_set_precision says, use no atomics, no spin
+ * and no dependency between workgroups, and add in a fixed order: two runs give the same bits.  Both launchers refuse bad
+ * arguments from host code before their first HIP call (AG_ERR_ARG).
+ *   ag_pitch_frames  x, ldx, lens, n_b and the framing exactly as ag_melcep_frames: frame j starts at sample 128 j, there are
+ *                    (n_b - 256) / 128 + 1 of them when n_b >= 256 and otherwise ONE; x[b, t] is never read for t >= n_b;
+ *                    F = the frame count of a clip of L samples is the capacity of the outputs; rows j >= nframes[b] are
+ *                    never written.  So frame j here is frame j of the cepstra and the path of ag_dtw_align indexes both.
+ *                    Constants: W = ag_pitch_window() = 256, TMIN = ag_pitch_tmin() = 20, TMAX = ag_pitch_tmax() = 127 (at
+ *                    8 kHz: 400 Hz down to 63 Hz); lags 19..128 are computed, 110 values.  Per frame:
+ *                      s[t]    = x[b, 128 j + t], t = 0..383; 0 (and not read) at and past n_b.  center != 0: the mean of
+ *                                the segment's valid samples (fp32, a fixed order of the kernel's own that depends on the
+ *                                segment alone) is subtracted from the valid samples; the zeros stay zero
+ *                      r(tau)  = sum_{t < 256} s[t] s[t + tau],  e(tau) = sum_{t < 256} s[t + tau]^2,  e0 = e(0): each sum
+ *                                ONE fmaf chain in ascending t
+ *                      phi(tau) = den > 0 ? r(tau) / sqrtf(den) : 0,  den = e0 * e(tau)  (sqrtf and the division correctly
+ *                                rounded)
+ *                      M       = max of phi over tau = 20..127
+ *                      tau*    = the SMALLEST tau in 20..127 with phi(tau) >= phi(tau - 1), phi(tau) >= phi(tau + 1) and
+ *                                phi(tau) >= octf * M (the product rounded once); 0 when M <= 0 or none qualifies - the
+ *                                first strong peak, which is what avoids octave errors
+ *                    -> lag[b, j] = tau* (int32 [B, F]); peak[b, j, 0..3] = phi(tau* - 1), phi(tau*), phi(tau* + 1), e0 / 256
+ *                    (fp32 [B, F, 4]; zeros and e0 / 256 when tau* = 0); nccf[b, j, 0..109] = phi(19..128), columns 110 and
+ *                    111 zero (fp32 [B, F, ag_pitch_nccf_width() = 112], NULL: not written); nframes_out[b] (int32, may be
+ *                    NULL).  The logarithm and the sub-sample refinement are the caller's, in float64
+ *                    (evaluate.pitch_cents).  One workgroup per (clip, tile of ag_pitch_tile() = 8 frames), one wave per
+ *                    frame, two lags a lane; a frame's bits do not depend on the tile it falls in.  The tile's samples are
+ *                    staged with 16-byte loads when x is 16-byte aligned and ldx is a multiple of 4
+ *                    ("pitch_frames_kernel<1>"), one float at a time otherwise ("pitch_frames_kernel<0>"): same bits.
+ *                    Refused: null x, lag or peak; B <= 0; L <= 0; ldx < L; octf outside (0, 1]; more than 65535 tiles a
+ *                    clip (L of 67 108 096 samples or more).
+ *   ag_pitch_path_accum  pc_a [B, Fa] (the rows of the alignment: the fake), pc_b [B, Fb] (the columns: the real clip):
+ *                    fp32 cents, NEGATIVE = unvoiced.  lo, hi int32 [B, Fb] as ag_dtw_align leaves them; m = clamp(nf_b[b],
+ *                    1, Fb) (NULL: Fb).  The path's cells are, for each column j < m, the rows lo[j]..hi[j], each cell once;
+ *                    row indices are clamped into [0, Fa - 1], so a wrong index is a wrong cell, never an address outside.
+ *                    Columns j >= m of lo, hi and pc_b are never read.  out[b, 0..4] (fp32 [B, ag_pitch_path_words() = 5],
+ *                    plain stores): the cells; the cells with both frames voiced; the cells whose voicing differs; the
+ *                    both-voiced cells with |a - b| > gross (cents); sum (a - b)^2 over the both-voiced cells.  The counts
+ *                    are integers until the store (exact: a path has at most 2047 cells).  The sum is one fmaf chain per
+ *                    column over ascending rows, then a fixed-order combination of the columns.  One workgroup of 256
+ *                    threads per pair.                                                   "pitch_path_accum_kernel"
+ *                    Refused: null pc_a, pc_b, lo, hi or out; B <= 0; Fa or Fb outside 1..1024.
+ * ------------------------------------------------------------------------- */
+int ag_pitch_window(void);
+int ag_pitch_tmin(void);
+int ag_pitch_tmax(void);
+int ag_pitch_nccf_width(void);
+int ag_pitch_tile(void);
+int ag_pitch_path_words(void);
+int ag_pitch_frames(const float* x, int64_t ldx, const int64_t* lens_i64, float octf, int center, int32_t* lag, float* peak,
+                    float* nccf, int32_t* nframes_out, int B, int L, void* stream);
+int ag_pitch_path_accum(const float* pc_a, const float* pc_b, const int32_t* lo, const int32_t* hi, const int32_t* nf_b,
+                        float gross, float* out, int B, int Fa, int Fb, void* stream);
+
+/* ---------------------------------------------------------------------------
  * ag_resample_poly (csrc/resample.hip): polyphase windowed-sinc resampling of ragged rows of PCM frames to the models'
  * rate (audio.resample, ingest.build_store).  Replaces librosa.load(wav, sr=8000) of the reference's preprocessing
  * (preprocess.py:24, preprocess-fisher.py:232).  fp32 whatever ag_set_precision says; no atomics, no workspace, one launch.
