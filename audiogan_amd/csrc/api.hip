@@ -210,6 +210,18 @@ static int slab_record(const float* ws, int Z, int64_t n, float* dst, int ncol, 
   return AG_OK;
 }
 
+// A write that is NOT recorded - the single-writer form of a reduction, a second stage issued while the scope is paused -
+// into floats that a recorded stage still has to write: the recorded stages run first (recording or paused alike), or the
+// two writes would land in the opposite order of their calls.
+int ag_slab_settle(const float* dst, int64_t span, hipStream_t st) {
+  for (int k = 0; k < g_multi.nd; ++k) {
+    const SlabDesc& E = g_multi.d[k];
+    const int64_t espan = (E.n / E.ncol - 1) * (int64_t)E.ld + E.ncol;
+    if (dst < E.dst + espan && E.dst < dst + span) return slab_flush(st);
+  }
+  return AG_OK;
+}
+
 // the second stage of a split-K product into a [M, N] block of row pitch ldc, inside a recording scope only
 int ag_slab_defer_2d(const float* ws, int Z, int M, int N, float* dst, int ldc, int accumulate, hipStream_t st) {
   return slab_record(ws, Z, (int64_t)M * N, dst, N, ldc, accumulate, st);
@@ -218,6 +230,8 @@ int ag_slab_defer_2d(const float* ws, int Z, int M, int N, float* dst, int ldc, 
 int ag_slab_reduce(const float* ws, int Z, int64_t n, float* dst, int accumulate, hipStream_t st) {
   if (n <= 0 || Z <= 0) return AG_OK;
   if (g_defer && n < ((int64_t)1 << 30)) return slab_record(ws, Z, n, dst, (int)n, (int)n, accumulate, st);
+  const int rc = ag_slab_settle(dst, n, st);
+  if (rc != AG_OK) return rc;
   if ((n & 3) == 0 && (((uintptr_t)ws | (uintptr_t)dst) & 15) == 0) {
     const int64_t n4 = n >> 2;
     hipLaunchKernelGGL(slab_reduce4_kernel, dim3((unsigned)ag_cdiv64(n4, 32)), dim3(256), 0, st, (const f32x4*)ws, Z, n4,

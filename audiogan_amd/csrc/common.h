@@ -51,6 +51,10 @@ int ag_slab_reduce(const float* ws, int Z, int64_t n, float* dst, int accumulate
 bool ag_reduces_deferred();   // inside a recording ag_defer_reduces scope (api.hip)
 // record (scope recording only) the second stage of a split-K product into a [M,N] block of row pitch ldc
 int ag_slab_defer_2d(const float* ws, int Z, int M, int N, float* dst, int ldc, int accumulate, hipStream_t st);
+// a reducing entry point is about to write the `span` floats from dst AT ONCE (a single-writer launch, or a second stage
+// that is not recorded): sum the recorded stages first if one of them covers any of those floats, so that the writes into
+// one destination keep the order of the calls.  Nothing recorded: nothing done.
+int ag_slab_settle(const float* dst, int64_t span, hipStream_t st);
 
 // C[row*ldc+col] = beta*C + sum_{z<Z} part[z*pitch + row*N+col] + bias[col] + res[row*ldres+col]   (gemm.hip)
 int ag_splitk_reduce(const float* part, int Z, int64_t pitch, int M, int N, float* C, int ldc, float beta,

@@ -737,6 +737,9 @@ extern "C" int ag_channel_sum(const float* dy, int64_t bs, int64_t cs, float* db
     AG_REQUIRE(ws.p && ws.numel >= 2 * (int64_t)C, "%s: this reduction spans several workgroups and needs a workspace of >= %lld floats bound with ag_bind_workspace (sums are two-stage, in a fixed order; there is no float-atomic accumulation)", "ag_channel_sum", (long long)2 * C);
     if ((int64_t)nsplit * C > ws.numel) nsplit = (int)(ws.numel / C);
     part = ws.p;
+  } else {
+    const int rc = ag_slab_settle(db, C, (hipStream_t)stream);
+    if (rc != AG_OK) return rc;
   }
   hipLaunchKernelGGL(channel_sum_kernel, dim3(C, nsplit), dim3(256), 0, (hipStream_t)stream, dy, bs,
                      cs, db, B, C, L, nsplit, part, accumulate);

@@ -555,6 +555,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
 int ag_splitk_reduce(const float* part, int Z, int64_t pitch, int M, int N, float* C, int ldc, float beta,
                      const float* bias, const float* res, int ldres, hipStream_t st) {
   const int64_t mn = (int64_t)M * N;
+  const int rc = ag_slab_settle(C, (int64_t)(M - 1) * ldc + N, st);
+  if (rc != AG_OK) return rc;
   hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)ag_cdiv64(mn, 32)), dim3(256), 0, st, part, Z, pitch, M, N,
                      C, ldc, beta, bias, res, ldres);
   AG_CHECK_LAUNCH("ag_splitk_reduce");
@@ -665,6 +667,10 @@ extern "C" int ag_gemm(const float* A, int lda, int ta, const float* B, int ldb,
     }
   }
   int rc;
+  if (!p.part) {      // the product itself writes C: a recorded stage for those floats goes first
+    rc = ag_slab_settle(C, (int64_t)(M - 1) * ldc + N, st);
+    if (rc != AG_OK) return rc;
+  }
   // bf16 mode: the bf16-MFMA kernel takes every shape with more than one row tile's worth of work whose operands
   // can be read 16 bytes at a time; the rest runs the fp32 kernels on operands rounded in registers
   // AG_PREC_F32X3: the same kernel in its split-bf16 form for the large products only (the others stay exact fp32)
@@ -744,6 +750,10 @@ extern "C" int ag_col_sum(const void* X, int x_bf16, int ldx, float* out, int M,
   const int rows_per = ag_cdiv(M, gy);
   gy = ag_cdiv(M, rows_per);
   if (gy == 1) part = nullptr;
+  if (!part) {
+    const int rc = ag_slab_settle(out, N, (hipStream_t)stream);
+    if (rc != AG_OK) return rc;
+  }
   hipLaunchKernelGGL(col_sum_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, (const float*)X, ldx, out, M,
                      N, rows_per, part, accumulate, x_bf16 ? 1 : 0);
   AG_CHECK_LAUNCH("ag_col_sum");

@@ -346,6 +346,10 @@ extern "C" int ag_gemm_h(const uint16_t* A, int lda, int ta, const uint16_t* B, 
       else p.kchunk = K;
     }
   }
+  if (!p.part && C) {      // the product itself writes C: a recorded stage for those floats goes first
+    const int rc = ag_slab_settle(C, (int64_t)(M - 1) * ldc + N, st);
+    if (rc != AG_OK) return rc;
+  }
   dim3 grid(ag_cdiv(N, 128), ag_cdiv(M, 128), p.ksplit);
   if (ta == 0 && tb == 0) launch_h<0, 0>(p, grid, st);
   if (ta == 0 && tb == 1) launch_h<0, 1>(p, grid, st);

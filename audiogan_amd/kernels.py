@@ -101,6 +101,9 @@ class deferred_reduces(object):
     gradients, bias / channel / column sums, split-K weight-gradient GEMMs called with ``defer=True``) run as ONE launch at
     the end instead of one each (ag_defer_reduces / ag_flush_reduces; same results bit for bit).  Nothing inside the block
     may read those outputs.  The partial-sum workspaces are kept alive until the flush.
+    A reducing call that writes at once into floats a recorded stage still has to write (a single-writer form, a
+    ``defer=False`` call) sums the recorded stages first, so one destination sees its writes in the order of the calls.
+    Kernels outside the reducing family (axpby, torch's own zero_, ...) remain the caller's business: flush_reduces() first.
     ``outer=True`` (common.network_backward): open a scope around a whole backward pass; it records only inside the
     Functions' own ``deferred_reduces()`` blocks, and those blocks then do NOT flush when they end - everything recorded
     by the whole backward is summed by one launch when the outer scope closes."""
